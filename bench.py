@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — decoded edges/s of a full sequential BVGraph successor scan on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Metric (BASELINE.json): decoded edges/s of a full sequential successor scan, plus the achieved
 fraction of the HBM-read roofline (algorithmic bytes = size of the .graph stream).
@@ -103,7 +103,10 @@ def main():
     ap.add_argument("--echo-ranks", action="store_true", help="plumbing test: every rank prints 'rank r of w' and exits before touching the GPU")
     ap.add_argument("--verify-whole", action="store_true", help="strong scaling: rank 0 also scans the whole graph in one piece (untimed) and compares it with the reduced {arcs, chk}")
     ap.add_argument("--one-device", action="store_true", help="rehearsal: every rank uses cuda:0 (needs --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned ({arcs, chk} of the step) as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -315,6 +318,8 @@ def main():
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tot_arcs, tot_chk)
     my_k_ms = float(np.mean(kernel_ms))
     if dist is not None:
         elapsed = S.allreduce_max(elapsed, device=cuda)
@@ -489,6 +494,17 @@ def self_launch(n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     return subprocess.call(cmd, env=env)
+
+
+def dump_outputs(d, arcs, chk):
+    """--dump-outputs: what the timed path returned in its last step -- the step's arc count and its 64-bit checksum (summed over the
+    ranks when there are several) -- as float64 .npy files, so that two builds can be compared on the same (seeded) workload.  arcs.npy
+    holds the count itself (exact: below 2^53).  chk_bits.npy holds the checksum's 64 bits, least significant first: a uint64 has no
+    exact float form, and as bits any difference is a difference of 1 whatever tolerance compares them."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "arcs.npy"), np.array([arcs], dtype=np.float64))
+    np.save(os.path.join(d, "chk_bits.npy"), np.array([(chk >> i) & 1 for i in range(64)], dtype=np.float64))
 
 
 def measured_pmc(shape, tiles, base_nodes, world, scaling):

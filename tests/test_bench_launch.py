@@ -49,3 +49,21 @@ def test_counter_figures_are_quoted_only_for_the_kernel_sources_they_were_measur
     assert (got is not None) == (e["src_id"] == sid)                            # quoted iff measured on THESE sources
     monkeypatch.setattr(bench, "kernel_source_id", lambda: "0" * 16)
     assert bench.measured_pmc(e["shape"], e["tiles"], e["base_nodes"], 1, "weak") is None
+
+
+def test_fewer_than_one_timed_step_is_an_error():
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0", "--echo-ranks"], capture_output=True, text=True, timeout=120, env=_env())
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+
+
+def test_dumped_outputs_hold_the_step_result_exactly(tmp_path):
+    """--dump-outputs: the arc count and every bit of the 64-bit checksum come back from the float64 files unchanged."""
+    import importlib
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    arcs, chk = 91_800_000_007, 0xF00DFACE_0000000B
+    bench.dump_outputs(str(tmp_path / "out"), arcs, chk)
+    a, b = np.load(str(tmp_path / "out" / "arcs.npy")), np.load(str(tmp_path / "out" / "chk_bits.npy"))
+    assert a.dtype == b.dtype == np.float64 and a.shape == (1,) and b.shape == (64,)
+    assert int(a[0]) == arcs and set(b.tolist()) <= {0.0, 1.0} and sum(int(v) << i for i, v in enumerate(b)) == chk
