@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define BVG_ABI_VERSION 3
+#define BVG_ABI_VERSION 4
 
 /* Status codes; each maps 1:1 to the exception class the reference throws at the cited line. */
 typedef enum bvg_status {
@@ -275,7 +275,13 @@ typedef struct bvg_tuning {
                                 ~4 KiB of stream: the lean scan kernel takes the block) but entries only for lists of >= 4 096 residuals --
                                 ~0.03 % of the stream instead of ~50 %; the residuals of a list are then one lane's walk.  Measured
                                 (profiles/r06_ab_marks_*.txt): eu15 stand-in 113 G edges/s (indexed 310, checking kernels 45), cnr-2000
-                                tiled 142 (151, 80).  An index that exists already is used as it is. */
+                                tiled 142 (151, 80).
+                                The index belongs to the graph, shared by every bvg_copy() flyweight, not to the handle that builds it: the mode
+                                (0 / 2) of the handle that builds it FIRST decides its granularity, and an index that exists already is used as it
+                                is.  A later scan outside it widens it to the whole graph in its own granularity and width, whatever the calling
+                                handle's mode; a handle of the other width (force_wide) never replaces it and scans without it.  Only when no good
+                                index exists (none yet, or its build failed) does the calling handle's mode decide.  Values above 2 are refused
+                                with BVG_E_ARG (ABI version 4). */
 } bvg_tuning;
 int bvg_set_tuning(bvg_graph* g, const bvg_tuning* t);
 
@@ -286,7 +292,8 @@ int bvg_abi_version(void);
  *   h  = (u32)x * 0x9E3779B1 + (u32)(x >> 32) * 0x85EBCA77;  h ^= h >> 15;  h *= 0x2C1B3C6D;  h ^= h >> 12     (mod 2^32)
  *   k1 = h | 1;   k0 = h * 0x297A2D39;  k0 ^= k0 >> 15                   (a per-node key, k1 odd; ten 32-bit operations)
  *   bvg_arc_mix(x, y) = k1 * y + k0                                      (mod 2^64)
- * chk = sum of bvg_arc_mix over all arcs, mod 2^64: commutative, so node-range shards reduce with
+ * chk = sum of bvg_arc_mix over all arcs, mod 2^64 (a successor missing from a list that came out short -- the -1 the decode reports
+ * whatever the node base -- counts as y + node_base = 2^64 - 1): commutative, so node-range shards reduce with
  * a plain sum (one RCCL all-reduce of {arcs, chk}).  Linear in y under the node's key: a kernel pays
  * one 32 x 32 + 64 multiply-add per successor (the reference's SpeedTest.java:127-135 does nothing
  * with them) and adds d * k0 per node.

@@ -735,7 +735,8 @@ int bvgo_scan(bvgo_graph* g, int64_t from, int64_t to, uint64_t node_base, bvgo_
         int64_t d = bvgo_iter_outdegree(it);
         const int64_t* s = bvgo_iter_successors(it);
         uint32_t k0, k1; node_key((uint64_t)x + node_base, &k0, &k1);
-        for (int64_t j = 0; j < d; j++) chk += mix_keyed(k0, k1, (uint64_t)s[j] + node_base);
+        /* a list that came out short is padded with -1 (BVG:1171): that arc is (x, -1) whatever the base, as the decode reports it (bvgraph_hip.h, checksum) */
+        for (int64_t j = 0; j < d; j++) chk += mix_keyed(k0, k1, s[j] < 0 ? ~0ull : (uint64_t)s[j] + node_base);
         arcs += (uint64_t)d; nodes++;
     }
     bvgo_iter_free(it);

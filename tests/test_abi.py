@@ -17,13 +17,17 @@ def _declared_functions():
     return sorted(set(re.findall(r"\b(bvg_[a-z_0-9]+)\s*\(", text)))
 
 
-def test_library_exports_every_declared_symbol(W):
+def test_library_exports_every_declared_symbol_at_abi_version_4(W):
+    """ABI version 4: bvg_set_tuning refuses bvg_tuning.no_index > 2.  The library, the header and the ctypes mirror agree on it."""
     lib = C.CDLL(W.build())
     names = _declared_functions()
     assert len(names) >= 20
     for n in names:
         assert hasattr(lib, n), "missing export: " + n
-    assert lib.bvg_abi_version() == 3
+    header = open(os.path.join(ROOT, "include", "bvgraph_hip.h")).read()
+    assert re.search(r"#define BVG_ABI_VERSION (\d+)", header).group(1) == "4"
+    assert lib.bvg_abi_version() == 4
+    assert W.lib().bvg_abi_version() == 4                                      # (the ctypes mirror loads it: its own version check passed)
 
 
 def test_struct_layouts_match_header(W):

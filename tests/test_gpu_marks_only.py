@@ -28,10 +28,11 @@ def test_marks_only_index_scans_with_the_lean_kernel(W, tools, oracle):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", ["residuals_only", "dense", "sparse"])
-def test_long_lists_without_entries_are_decoded_by_the_whole_wavefront(W, tools, oracle, kind):
-    """Marks only: lists of more than 32 residuals have no skip entries; behind their first 32 residuals the wavefront decodes them together, 64 bit positions of the stream per
-    step (bvg_scan.hip, "COOP": every lane decodes the code that would start at its bit, a scalar walk over the lengths marks the real starts, a wave prefix sum gives the values).
-    Leaves (window 0: nothing is copied), stored lists with and without reference, lists merged straight into the output of decode_range."""
+def test_long_lists_without_entries_match_the_oracle(W, tools, oracle, kind):
+    """Marks only: lists below 4 096 residuals have no skip entries, so the residual pass cannot cut them into segments: each such list is ONE task, walked
+    residual by residual by one lane (bvg_scan.hip, residual tasks), on validated blocks of the lean kernel.  Scans (whole graph and sub-ranges) and the
+    materialised lists must still equal the oracle's: leaves (window 0: nothing is copied), stored lists with and without reference, lists merged straight
+    into the output of decode_range."""
     if kind == "residuals_only": st = tools.synth_store(12000, seed=21, params=W.default_params(window_size=0, max_ref_count=0), synth=tools.eu_like(mean_deg=90.0), threads=4)
     elif kind == "dense": st = tools.synth_store(20000, seed=22, synth=tools.eu_like(mean_deg=120.0), threads=4)
     else: st = tools.synth_store(30000, seed=23, synth=tools.web_like(), threads=4)

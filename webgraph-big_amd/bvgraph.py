@@ -147,7 +147,7 @@ def lib():
         L.bvg_build_index.argtypes = [vp, i64, i64, C.POINTER(u64), C.POINTER(u64)]
         L.bvg_save_index.argtypes = [vp, C.c_char_p]
         L.bvg_load_index.argtypes = [vp, C.c_char_p]
-        if L.bvg_abi_version() != 3:
+        if L.bvg_abi_version() != 4:
             raise ImportError("libbvgraph_hip.so ABI mismatch")
         _LIB = L
     return _LIB

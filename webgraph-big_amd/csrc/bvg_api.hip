@@ -175,7 +175,7 @@ void bvg_close(bvg_graph* g) {
 
 int bvg_info(const bvg_graph* g, bvg_params* out) { if (!g || !out) return BVG_E_ARG; *out = g->sh->p; return 0; }
 int bvg_set_node_base(bvg_graph* g, uint64_t node_base) { if (!g) return BVG_E_ARG; g->node_base = node_base; return 0; }
-int bvg_set_tuning(bvg_graph* g, const bvg_tuning* t) { if (!g || !t) return BVG_E_ARG; g->tun = *t; return 0; }
+int bvg_set_tuning(bvg_graph* g, const bvg_tuning* t) { if (!g || !t || t->no_index > 2) return BVG_E_ARG; g->tun = *t; return 0; }
 
 int bvg_get_offsets(bvg_graph* g, uint64_t* out) {
     if (!g || !out) return BVG_E_ARG;

@@ -34,10 +34,18 @@ int build_skip(bvg_graph* g, const std::shared_ptr<Plan>& plp, uint32_t blo, uin
     Shared* sh = g->sh;
     std::lock_guard<std::mutex> lk(sh->skip_mu);
     Plan& pl = *plp;
+    // The index belongs to the graph, not to the handle that happens to build it: once a good one exists, its width and granularity are the graph's.  A second range
+    // widens it to the whole graph in that same form -- whatever the calling handle's mode (bvg_tuning.no_index 0 / 2) -- and a handle of the other width
+    // (bvg_tuning.force_wide) does not replace it: it scans index-less, as it does over a covering index of the other width.  Only when no good index exists (none yet,
+    // or the build failed) does the caller's mode decide.
+    std::shared_ptr<SkipIndex> good;
     {
         std::shared_ptr<SkipIndex> cur = std::atomic_load(&pl.skip);
         if (cur && !(cur->failed && retry_failed) && cur->covers(blo, bhi)) return 0;   // another thread built it meanwhile (or failed to: not tried again here)
-        if (cur && !cur->failed) { blo = 0; bhi = pl.nblk; first_scan = nullptr; }   // a second range: index the whole graph once and for all (the scan's own range is a part of it: it scans afterwards)
+        if (cur && !cur->failed) {
+            if (cur->wide != (sh->wide || g->tun.force_wide)) return 0;
+            good = cur; blo = 0; bhi = pl.nblk; first_scan = nullptr;             // a second range: index the whole graph once and for all (the scan's own range is a part of it: it scans afterwards)
+        }
     }
     const uint32_t nblk = pl.nblk;
     if (!nblk || sh->p.nodes == 0 || blo >= bhi) return 0;
@@ -49,6 +57,7 @@ int build_skip(bvg_graph* g, const std::shared_ptr<Plan>& plp, uint32_t blo, uin
     // bvg_tuning.no_index = 2 ("marks only", round 6): the validating pass and its marks -- one byte per block, what lets the lean scan kernel take the block -- but entries
     // only for lists of 4 096 residuals and more (one per 64: the giant kernel's lists, which it cannot walk in step at any useful rate): an index of ~0.03 % of the stream
     if (g->tun.no_index == 2) { ix->skip_min = 4096; ix->skip_shift = 6; }
+    if (good) { ix->skip_min = good->skip_min; ix->skip_shift = good->skip_shift; }
     auto publish = [&]() { std::atomic_store(&pl.skip, ix); return 0; };
     // no index: the scans run without one.  The failure is PUBLISHED (an empty snapshot of the same block range, unless a good index of
     // other blocks exists already), so that later scans of these blocks do not pay the counting pass again and again; bvg_build_index() retries.
@@ -273,10 +282,12 @@ int load_index_impl(bvg_graph* g, const char* path) {
     acc = fold_hash(acc, host_hash(pl.h_first.data(), (nb + 1) * 8), 1); acc = fold_hash(acc, host_hash(pl.h_maxd.data(), nb * 4), 2);
     if (hipMalloc(&pl.d_first, (nb + 1) * 8) != hipSuccess || hipMalloc(&pl.d_halo, nb * 4) != hipSuccess || hipMalloc(&pl.d_mask, nb * 8) != hipSuccess) { (void)hipGetLastError(); return BVG_E_NOMEM; }
     HIPCHK(hipMemcpy(pl.d_first, pl.h_first.data(), (nb + 1) * 8, hipMemcpyHostToDevice));
-    {   // halos: range-checked on the host on their way in (a halo reaches at most kMaxHalo nodes back and never before node 0)
+    {   // halos: range-checked on the host on their way in (a halo reaches at most kMaxHalo nodes back -- kMaxHaloBig for windows > kMaxWindow, bvg_kernels.h --
+        // and never before node 0)
         std::vector<uint32_t> halo(nb);
         if (fread(halo.data(), 4, nb, f) != nb) return BVG_E_IO;
-        for (size_t i = 0; i < nb; i++) if (halo[i] > (uint32_t)kMaxHalo || (uint64_t)halo[i] > pl.h_first[i]) return BVG_E_IO;
+        const uint32_t max_halo = sh->p.window_size > kMaxWindow ? (uint32_t)kMaxHaloBig : (uint32_t)kMaxHalo;
+        for (size_t i = 0; i < nb; i++) if (halo[i] > max_halo || (uint64_t)halo[i] > pl.h_first[i]) return BVG_E_IO;
         HIPCHK(hipMemcpy(pl.d_halo, halo.data(), nb * 4, hipMemcpyHostToDevice));
         acc = fold_hash(acc, host_hash(halo.data(), nb * 4), 3);
     }

@@ -41,6 +41,7 @@ int run_decode(bvg_graph* g, int64_t from, int64_t to, bool materialise, const u
         // (round 6: the cause is the covering RANGE's own, and only a call that could rebuild -- a scan, or a materialising call of a quarter of the graph -- counts down)
         const bool can_build = !materialise || (to - from) >= sh->p.nodes / 4;
         if (cur && covered && cur->failed && cur->cause_of(lo, lo + nblocks) == SkipIndex::kResources) { if (can_build && tick(*cur) <= 1) { covered = false; retry = true; } }
+        else if (cur && !covered && !cur->failed && cur->wide != wide) covered = true;        // a good index of the other width is not replaced (build_skip): this handle scans without it
         else if (cur && !covered && !cur->failed && can_build && tick(*cur) > 0) covered = true;
         if (!covered && (!materialise || (to - from) >= sh->p.nodes / 4)) {
             bool scanned = false;
