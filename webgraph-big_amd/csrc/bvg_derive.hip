@@ -316,7 +316,7 @@ int derive_offsets_parallel(const uint8_t* graph, uint64_t nbytes, int64_t n, in
     const uint64_t nch64 = (total_bits + kChunkBits - 1) / kChunkBits;
     if (nch64 > 0x7FFFFFF0ull) return -1;
     const uint32_t nchunks = (uint32_t)nch64, R = (uint32_t)window + 1u;
-    const bool gen = !(cod.outdegree == BVG_GAMMA && cod.reference == BVG_UNARY && cod.block_count == BVG_GAMMA && cod.block == BVG_GAMMA && cod.residual == BVG_ZETA);
+    const bool gen = !is_default_codings(cod);
     struct Bufs {
         std::vector<void*> p;
         void* get(size_t bytes) { void* q = nullptr; if (hipMalloc(&q, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); return nullptr; } p.push_back(q); return q; }

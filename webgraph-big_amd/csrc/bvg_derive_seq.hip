@@ -112,8 +112,7 @@ __global__ void __launch_bounds__(64) derive_offsets_kernel(const uint8_t* graph
 
 void launch_derive_offsets(const uint8_t* graph, uint64_t padded_bytes, uint64_t nbytes, int64_t n, int window, int min_interval, Codings cod,
                            uint64_t* offsets, unsigned* err, hipStream_t s) {
-    const bool gen = !(cod.outdegree == BVG_GAMMA && cod.reference == BVG_UNARY && cod.block_count == BVG_GAMMA &&
-                       cod.block == BVG_GAMMA && cod.residual == BVG_ZETA);
+    const bool gen = !is_default_codings(cod);
     if (gen) hipLaunchKernelGGL((derive_offsets_kernel<true>), dim3(1), dim3(64), 0, s, graph, padded_bytes, nbytes, n, window, min_interval, cod, offsets, err);
     else hipLaunchKernelGGL((derive_offsets_kernel<false>), dim3(1), dim3(64), 0, s, graph, padded_bytes, nbytes, n, window, min_interval, cod, offsets, err);
 }

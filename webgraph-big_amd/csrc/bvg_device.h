@@ -26,6 +26,10 @@ struct Codings {
     int outdegree, block, residual, reference, block_count;
     int zeta_k;
 };
+// BVGraph's default codings (gamma outdegrees, unary references, gamma blocks and block counts, zeta residuals): the specialised kernels' only case
+__host__ __device__ inline bool is_default_codings(const Codings& c) {
+    return c.outdegree == BVG_GAMMA && c.reference == BVG_UNARY && c.block_count == BVG_GAMMA && c.block == BVG_GAMMA && c.residual == BVG_ZETA;
+}
 
 // A cursor over the .graph bytes in global memory.  `limit_byte` is the last byte index that may be
 // the start of an 8-byte load (the buffer is padded); positions beyond read as the padding zeros.

@@ -158,7 +158,7 @@ __global__ void __launch_bounds__(GNT, BVG_GIANT_MINWG) giant_kernel(DecodeArgs 
     uint64_t chk = 0, blk_arcs = 0, blk_nodes = 0;             // chk: per thread; arcs / nodes: uniform
     unsigned err = 0;
     bool failed = false;
-    uint32_t fail_need = 0xFFFFFFF5u;
+    uint32_t fail_need = kFailCode;
     uint64_t cur = 0;                                          // bit cursor of the walk in step (uniform)
 
     // The walk in step is WAVEFRONT 0's alone (the scalar unit is shared by the four SIMDs of a CU: four wavefronts walking in step
@@ -256,20 +256,20 @@ __global__ void __launch_bounds__(GNT, BVG_GIANT_MINWG) giant_kernel(DecodeArgs 
             uint32_t hfail = 0;
             do {
                 seek(off_x);
-                if (!rd_gamma(v) || v > 0x7FFFFFFFull) { hfail = 0xFFFFFFF5u; break; }
+                if (!rd_gamma(v) || v > 0x7FFFFFFFull) { hfail = kFailCode; break; }
                 d = (uint32_t)v;
                 if (d == 0) break;
                 if (W > 0) {                                                   // readReference (unary), BVG:692-703
                     const uint32_t lz = sclz64(hi);
-                    if (lz >= 63u) { hfail = 0xFFFFFFF5u; break; }
+                    if (lz >= 63u) { hfail = kFailCode; break; }
                     consume(lz + 1); v = lz;
                     if (v > W || (int64_t)v > x) { err |= ERR_REF_RANGE; v = 0; }
                     ref = (uint32_t)v;
                 }
                 if (ref > 0) {
-                    if (!rd_gamma(v) || v > rec_end - (cur < rec_end ? cur : rec_end) + 1) { hfail = 0xFFFFFFF5u; break; }
+                    if (!rd_gamma(v) || v > rec_end - (cur < rec_end ? cur : rec_end) + 1) { hfail = kFailCode; break; }
                     bc = (uint32_t)v;
-                    if ((uint64_t)bc + 4 > SCR) { hfail = 0xFFFFFFF2u; break; }
+                    if ((uint64_t)bc + 4 > SCR) { hfail = kFailHuge; break; }
                 }
             } while (0);
             if (lane == 0) { hd[0] = d; hd[1] = ref; hd[2] = bc; hd[6] = hfail; hd[7] = (uint32_t)cur; hd[8] = (uint32_t)(cur >> 32); }
@@ -370,8 +370,8 @@ __global__ void __launch_bounds__(GNT, BVG_GIANT_MINWG) giant_kernel(DecodeArgs 
             if (wv == 0) {
                 uint32_t hfail = 0;
                 seek(cur);
-                if (!rd_gamma(v) || v > (rec_end - (cur < rec_end ? cur : rec_end)) / 2 + 1) hfail = 0xFFFFFFF5u;
-                else if (ib + 3ull * v + 4 > SCR) hfail = 0xFFFFFFF2u;
+                if (!rd_gamma(v) || v > (rec_end - (cur < rec_end ? cur : rec_end)) / 2 + 1) hfail = kFailCode;
+                else if (ib + 3ull * v + 4 > SCR) hfail = kFailHuge;
                 if (lane == 0) { hd[3] = hfail ? 0u : (uint32_t)v; hd[6] = hfail; hd[7] = (uint32_t)cur; hd[8] = (uint32_t)(cur >> 32); }
             }
             __syncthreads();
@@ -521,7 +521,7 @@ __global__ void __launch_bounds__(GNT, BVG_GIANT_MINWG) giant_kernel(DecodeArgs 
             __syncthreads();
             if (ref > 0) rlb = nd_base[(uint32_t)(x - ref) & RM];
         }
-        if (pool_used + (uint64_t)d + nres + 1 > CAP) { failed = true; GP_WHY(10); fail_need = 0xFFFFFFF2u; break; }
+        if (pool_used + (uint64_t)d + nres + 1 > CAP) { failed = true; GP_WHY(10); fail_need = kFailHuge; break; }
         const uint64_t base = pool_used;
         T* const out = pool + base;
         T* const rt = pool + (CAP - nres - 1);

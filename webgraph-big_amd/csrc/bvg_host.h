@@ -164,7 +164,10 @@ struct bvg_graph {
     int skip_mode = 0; uint32_t* skip_cnt = nullptr;   // transient: set while this handle builds the skip index
     std::shared_ptr<SkipIndex> skip_building;          // transient: the index the fill pass (skip_mode 2) writes
     struct Pred {
-        uint64_t plan_version = 0, skip_gen = 0; uint32_t lo = 0, n = 0, pool0 = 0, mode = 0; uint32_t* d_lists = nullptr; uint32_t count[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; uint64_t giant_need = 0;
+        // the work lists, one after another in d_lists: the row kernel's tier 0 and LDS classes 1-4, giants, the generic kernel, the lean scan kernel's tier 0 and classes 1-4
+        enum Slot : int { kRow0, kRowC1, kRowC2, kRowC3, kRowC4, kGiant, kGeneric, kLean0, kLeanC1, kLeanC2, kLeanC3, kLeanC4, kSlots };
+        uint64_t plan_version = 0, skip_gen = 0; uint32_t lo = 0, n = 0, pool0 = 0, mode = 0; uint32_t* d_lists = nullptr; uint32_t count[kSlots] = {}; uint64_t giant_need = 0;
+        size_t offset(int slot) const { size_t o = 0; for (int c = 0; c < slot; c++) o += count[c]; return o; }   // of the slot's list in d_lists
         std::vector<uint8_t> learned; std::vector<uint8_t> leanfail; uint64_t learned_version = 0, learned_gen = 0; uint32_t learned_pool0 = 0, learned_mode = 0; bool dirty = false;   // tier in which a mispredicted block finally succeeded: the next scans send it there directly
     } pred2[2];                                      // [0] scans, [1] materialising calls (round 6: a handle that alternates bvg_scan and bvg_decode_range keeps what it learned for each; one slot made every change of mode start from the prediction again)
 };

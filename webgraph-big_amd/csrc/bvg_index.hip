@@ -182,7 +182,7 @@ void launch_clear_unmarked_entries(const uint64_t* first, const uint8_t* fmt, ui
 // fills the entries of the blocks of the work list (or of blk_lo + [0, nblocks)); `wide`: 64-bit entry values
 void launch_index_walk(const DecodeArgs& a, uint32_t nblocks, bool wide, hipStream_t s) {
     if (nblocks == 0) return;
-    const bool gen = !(a.cod.outdegree == BVG_GAMMA && a.cod.reference == BVG_UNARY && a.cod.block_count == BVG_GAMMA && a.cod.block == BVG_GAMMA && a.cod.residual == BVG_ZETA);
+    const bool gen = !is_default_codings(a.cod);
     const dim3 grid(nblocks), block(64);
     if (wide) { if (gen) hipLaunchKernelGGL((index_walk_kernel<uint64_t, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((index_walk_kernel<uint64_t, false>), grid, block, 0, s, a); }
     else { if (gen) hipLaunchKernelGGL((index_walk_kernel<uint32_t, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((index_walk_kernel<uint32_t, false>), grid, block, 0, s, a); }

@@ -15,6 +15,17 @@ namespace bvg {
 inline const char* knob(const char* name) { static const bool live = getenv("BVG_TEST_KNOBS") != nullptr; return live ? getenv(name) : nullptr; }
 inline bool dbg_on() { static const bool on = getenv("BVG_DEBUG") != nullptr; return on || knob("BVG_DEBUG") != nullptr; }
 
+// DecodeArgs::fail_need of a failed block: the list-pool elements it would need, or (kFailReason and up) why it failed otherwise
+enum : uint32_t {
+    kFailReason = 0xFFFFFFF0u,          // below: a pool need
+    kFailWindow = 0xFFFFFFF1u,          // a single record larger than the window
+    kFailHuge = 0xFFFFFFF2u,            // a list too large for any LDS pool / the global-memory area too small
+    kFailBlocks = 0xFFFFFFF3u,          // one node's copy blocks exceed the scratch area
+    kFailIntervals = 0xFFFFFFF4u,       // one node's intervals exceed the scratch area
+    kFailCode = 0xFFFFFFF5u,            // a bad code, or the skip index out of step with the stream
+    kFailUnknown = 0xFFFFFFFFu,         // need unknown
+};
+
 // LDS geometry of the fast (one wavefront per node block) decode kernel.
 #ifndef BVG_SKIP_MIN
 #define BVG_SKIP_MIN 16
@@ -77,7 +88,7 @@ struct DecodeArgs {
     int64_t* succ; int32_t* outdeg;
     // slow path hand-off
     uint32_t* fail_list; uint32_t* fail_count; uint32_t fail_cap;
-    uint32_t* fail_need;                // per failed block: list-pool elements it would need (0xFFFFFFFF = unknown / other cause)
+    uint32_t* fail_need;                // per failed block: list-pool elements it would need, or one of the kFail* reasons below
     // slow-path pools (global memory), per workgroup
     void* gpool; uint64_t gpool_elems; void* gscr; uint64_t gscr_elems;
     // giant kernel: the work areas are SLOTS shared by the whole launch (as many as workgroups can be resident, not one per block): a workgroup takes a free
@@ -121,7 +132,7 @@ int derive_offsets_parallel(const uint8_t* graph, uint64_t nbytes, int64_t n, in
 
 // Experiments that lost to the row kernel are compiled only by `make experimental` (-DBVG_EXPERIMENTAL): the row kernel
 // with one workgroup of nw wavefronts per block sharing the pool (bvg_rows_wg.hip), the streaming data-flow kernel
-// (bvg_stream.hip), the flow scan kernel (bvg_flow.hip), 
+// (bvg_stream.hip), the flow scan kernel (bvg_flow.hip) and the flat scan kernel (bvg_flat.hip)
 #ifdef BVG_EXPERIMENTAL
 constexpr bool kExperimental = true;
 void launch_rows_wg_decode(const DecodeArgs& a, uint32_t nblocks, int nw, hipStream_t s);
@@ -138,6 +149,7 @@ size_t flat_table_bytes(uint32_t recs, int window);
 constexpr bool kExperimental = false;
 inline void launch_rows_wg_decode(const DecodeArgs&, uint32_t, int, hipStream_t) {}
 inline size_t rows_wg_static_lds(int) { return 0; }
+inline void launch_stream_decode(const DecodeArgs&, uint32_t, bool, bool, hipStream_t) {}
 inline size_t flow_scratch_bytes_per_wave(int) { return 0; }
 inline size_t flow_lds_bytes(uint32_t) { return 0; }
 inline void launch_flow_scan(const DecodeArgs&, uint32_t, uint32_t, void*, uint32_t, hipStream_t) {}

@@ -571,8 +571,7 @@ __global__ void unpack_offsets_kernel(Offsets o, int64_t first, int64_t count, u
 void launch_decode(const DecodeArgs& a, uint32_t nblocks, bool wide, bool materialise, bool slow, hipStream_t s) {
     if (nblocks == 0) return;
     dim3 grid(nblocks), block(64);
-    const bool gen = !(a.cod.outdegree == BVG_GAMMA && a.cod.reference == BVG_UNARY && a.cod.block_count == BVG_GAMMA &&
-                       a.cod.block == BVG_GAMMA && a.cod.residual == BVG_ZETA);
+    const bool gen = !is_default_codings(a.cod);
     const size_t dyn = (slow ? 0 : (size_t)(a.lds_pool_elems + a.lds_scr_elems) * (wide ? 8 : 4)) + (size_t)a.lds_stage_words * 4;
     if (a.window > kMaxWindow) {                                              // wide windows: global-memory tier only, big node ring
         if (!slow) return;

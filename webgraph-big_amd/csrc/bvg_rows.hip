@@ -87,7 +87,7 @@ __global__ void __launch_bounds__(64, TASK ? BVG_TASK_WAVES : BVG_ROWS_WAVES) ro
     uint64_t blk_arcs = 0, blk_chk = 0, blk_nodes = 0;
     unsigned err = 0;
     bool failed = false;
-    uint32_t fail_need = 0xFFFFFFFFu;                        // pool elements that would have been enough (when known)
+    uint32_t fail_need = kFailUnknown;                       // pool elements that would have been enough (when known)
     uint32_t cnt_iter = 0, cnt_pass = 0, cnt_rows = 0, cnt_tasks = 0, cnt_seek = 0, cnt_leaf = 0, cnt_leafp = 0;   // BVG_DBG & 64: work counters (wave-uniform)
     // -DBVG_PROF builds only (`make prof`): wave-cycles per section {row prep, level prep, task set-up, seeks, merge loop,
     // phase 1, row set-up, headers, pool sizing, residuals}, reported with BVG_DBG & 64.  Off by default: the accumulators cost
@@ -178,7 +178,7 @@ __global__ void __launch_bounds__(64, TASK ? BVG_TASK_WAVES : BVG_ROWS_WAVES) ro
             kwin = m == ~0ull ? 64u : (uint32_t)__ffsll((unsigned long long)~m) - 1u;
             if (kwin > left) kwin = left;
         }
-        if (kwin == 0) { failed = true; fail_need = 0xFFFFFFF1u; break; }      // a single record larger than the window
+        if (kwin == 0) { failed = true; fail_need = kFailWindow; break; }      // a single record larger than the window
         uint32_t rel = (uint32_t)(off_x - stg_bit0);                          // bit cursor relative to the window
         const uint32_t pend = (uint32_t)(rec_end - stg_bit0);
         bool bad = false;
@@ -235,7 +235,7 @@ __global__ void __launch_bounds__(64, TASK ? BVG_TASK_WAVES : BVG_ROWS_WAVES) ro
         }
         const uint32_t bincl = wave_incl_scan32(bc > SCR ? SCR + 1 : bc);
         { const uint32_t kb = (uint32_t)__popcll(ballot(bincl <= SCR)); k = kb < k ? kb : k; }
-        if (k == 0) { failed = true; fail_need = 0xFFFFFFF3u; break; }        // one node's copy blocks exceed the scratch area
+        if (k == 0) { failed = true; fail_need = kFailBlocks; break; }        // one node's copy blocks exceed the scratch area
         sb = bincl - bc;
         uint32_t btot = lane_get(bincl, k - 1);
         // ---- B: copy blocks (BVG:1023-1032) and C: interval count (BVG:1040)
@@ -272,7 +272,7 @@ __global__ void __launch_bounds__(64, TASK ? BVG_TASK_WAVES : BVG_ROWS_WAVES) ro
             if (ki != 0 || k <= 1) { k = ki < k ? ki : k; break; }
             k = (k + 1u) >> 1; btot = lane_get(bincl, k - 1);
         }
-        if (k == 0) { failed = true; fail_need = 0xFFFFFFF4u; break; }        // one node's intervals exceed the scratch area
+        if (k == 0) { failed = true; fail_need = kFailIntervals; break; }     // one node's intervals exceed the scratch area
         ib = btot + iincl - iw;
         // ---- D1: intervals (BVG:1042-1058): they fix the number of residuals
         if (parse && lane < k) {
@@ -331,7 +331,7 @@ __global__ void __launch_bounds__(64, TASK ? BVG_TASK_WAVES : BVG_ROWS_WAVES) ro
             {
                 uint32_t d0 = lane_get(d, 0); const uint32_t n0 = lane_get(nres, 0);
                 if (TASK && d0 <= 0x3FFFFFFFu) d0 += (n0 > d0 ? d0 : n0) + 1u;
-                fail_need = d0 > 0x3FFFFFFFu ? 0xFFFFFFF2u : d0 + pool_used + (d0 >> 2) + 64 + SWE;
+                fail_need = d0 > 0x3FFFFFFFu ? kFailHuge : d0 + pool_used + (d0 >> 2) + 64 + SWE;
             }
             break;
         }
@@ -360,7 +360,7 @@ __global__ void __launch_bounds__(64, TASK ? BVG_TASK_WAVES : BVG_ROWS_WAVES) ro
         const uint32_t rdst = TASK ? rtb : base + size - nres;
         if ((a.skip_mode == 0 || a.skip_mode == 3) && sk_n != 0 && ballot(cntE != 0) && !(a.dbg & 2)) {   // (3: the validating pass of the index build decodes WITH the entries the dense walk has just written, and checks every one of them)
             // long residual lists are cut at their skip entries: every segment of <= kSkipEvery gaps is one task
-            if (sk_run > sk_n) { failed = true; fail_need = 0xFFFFFFF5u; break; }      // index out of step with the stream
+            if (sk_run > sk_n) { failed = true; fail_need = kFailCode; break; }        // index out of step with the stream
             // long tasks first (full segments and tails of more than kShortTask gaps), the short tails after them: a pass of 64
             // tasks lasts as long as its longest one, so like goes with like
             const bool hasres = parse && lane < k && nres > 0 && !bad;
@@ -464,7 +464,7 @@ __global__ void __launch_bounds__(64, TASK ? BVG_TASK_WAVES : BVG_ROWS_WAVES) ro
             if (kResUnroll >= 2 && Ttot > 96u) task_passes(std::integral_constant<uint32_t, 2>{}); else task_passes(std::integral_constant<uint32_t, 1>{});
             if (((act && d == 0) || (parse && lane < k && nres == 0)) && rel != pend && !bad && !(a.dbg & 7u)) err |= ERR_MALFORMED;
             bad |= tbad;
-            if (ballot(tbad)) { failed = true; fail_need = 0xFFFFFFF5u; break; }
+            if (ballot(tbad)) { failed = true; fail_need = kFailCode; break; }
         } else if (parse && lane < k) {
             if (nres > 0 && !bad && !(a.dbg & 2)) {
                 T* const tail = pool + rdst;
@@ -487,7 +487,7 @@ __global__ void __launch_bounds__(64, TASK ? BVG_TASK_WAVES : BVG_ROWS_WAVES) ro
             }
             if (rel != pend && !bad && !(a.dbg & 7u)) err |= ERR_MALFORMED;         // SURVEY A.6 self-check
         } else if (act && d == 0 && rel != pend && !bad) err |= ERR_MALFORMED;
-        if (ballot(bad && lane < k)) { failed = true; fail_need = 0xFFFFFFF5u; break; }
+        if (ballot(bad && lane < k)) { failed = true; fail_need = kFailCode; break; }
         wave_sync();
 
         // ------------------------------------------------------------------ phase 2: data-flow emission
@@ -781,7 +781,7 @@ __global__ void __launch_bounds__(64, TASK ? BVG_TASK_WAVES : BVG_ROWS_WAVES) ro
             }
             BVG_T1(10, tqL);
             if (by_tasks) {
-                if (ballot(zbad)) { failed = true; fail_need = 0xFFFFFFF5u; break; }
+                if (ballot(zbad)) { failed = true; fail_need = kFailCode; break; }
                 if (rep) { blk_arcs += d; blk_nodes += 1; if (!MAT) blk_chk += mix_node_const(k0, k1, a.node_base, d); }
             }
         }
@@ -903,8 +903,7 @@ __global__ void __launch_bounds__(64, TASK ? BVG_TASK_WAVES : BVG_ROWS_WAVES) ro
 void launch_rows_decode(const DecodeArgs& a, uint32_t nblocks, bool wide, bool materialise, hipStream_t s) {
     if (nblocks == 0) return;
     dim3 grid(nblocks), block(64);
-    const bool gen = !(a.cod.outdegree == BVG_GAMMA && a.cod.reference == BVG_UNARY && a.cod.block_count == BVG_GAMMA &&
-                       a.cod.block == BVG_GAMMA && a.cod.residual == BVG_ZETA);
+    const bool gen = !is_default_codings(a.cod);
     const bool task0 = a.emit_tasks != 0;
     size_t dyn = (size_t)(a.lds_pool_elems + a.lds_scr_elems) * (wide ? 8 : 4) + (task0 ? 0 : (size_t)a.lds_stage_words * 4);   // (task variant: the window lies inside the pool)
     if (knob("BVG_LDSPAD")) dyn += (size_t)atoi(knob("BVG_LDSPAD"));   // occupancy experiments: unused LDS behind the window

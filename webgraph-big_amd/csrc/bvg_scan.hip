@@ -237,7 +237,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
     uint64_t blk_arcs = 0, blk_chk = 0, blk_nodes = 0;
     unsigned err = 0;
     bool failed = false;
-    uint32_t fail_need = 0xFFFFFFFFu;                        // pool elements that would have been enough (when known)
+    uint32_t fail_need = kFailUnknown;                       // pool elements that would have been enough (when known)
     uint32_t cnt_super = 0, cnt_sub = 0, cnt_nodes = 0;      // BVG_DBG & 64: work counters (wave-uniform)
     // -DBVG_PROF builds only (`make prof`): wave-cycles per section, reported with BVG_DBG & 64 through the row kernel's counters
     // {0 descriptors + levels, 1 Z2 sizing, 2 Z2 set-up, 3 Z1, 4 Z2 loop, 5 phase 1, 6 row set-up, 7 headers, 8 pool sizing, 9 residuals, 10 leaf pass, 11 leaf loop}
@@ -345,7 +345,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
             K1 = m == ~0ull ? 64u : (uint32_t)__ffsll((unsigned long long)~m) - 1u;
             if (K1 > left) K1 = left;
         }
-        if (K1 == 0) { failed = true; fail_need = 0xFFFFFFF1u; break; }       // a single record larger than the window
+        if (K1 == 0) { failed = true; fail_need = kFailWindow; break; }       // a single record larger than the window
         // prefetch the next super-row's offsets now (their latency hides behind the header parse); the scratch area may still cut
         // this super-row shorter, then they are fetched again below
         const uint32_t K1win = K1;
@@ -412,7 +412,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
         const uint32_t SCRH = (CAP - pool_used) >> 1;                         // at most half of what the lists carried over leave free
         const uint32_t bincl = wave_incl_scan32(bc > SCRH ? SCRH + 1 : bc);
         { const uint32_t kb = (uint32_t)__popcll(ballot(bincl <= SCRH)); K1 = kb < K1 ? kb : K1; }
-        if (K1 == 0) { failed = true; fail_need = 0xFFFFFFF3u; break; }       // one node's copy blocks exceed the scratch area
+        if (K1 == 0) { failed = true; fail_need = kFailBlocks; break; }       // one node's copy blocks exceed the scratch area
         const uint32_t btot = lane_get(bincl, K1 - 1);                        // (stays, should the intervals cut the super-row shorter: the blocks are written by then)
         const uint32_t bbase = CAP - btot;
         sb = bbase + bincl - bc;
@@ -513,7 +513,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
             if (ki != 0 || K1 <= 1) { K1 = ki < K1 ? ki : K1; break; }
             K1 = (K1 + 1u) >> 1;
         }
-        if (K1 == 0) { failed = true; fail_need = 0xFFFFFFF4u; break; }       // one node's intervals exceed the scratch area
+        if (K1 == 0) { failed = true; fail_need = kFailIntervals; break; }    // one node's intervals exceed the scratch area
         const uint32_t itot = lane_get(iincl, K1 - 1);
         const uint32_t CAPe = bbase - itot;                                   // what is left for the lists and the parked residuals of this super-row's sub-rows
         ib = CAPe + iincl - iw;
@@ -578,7 +578,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
 #ifdef BVG_EXP_PRIO
         __builtin_amdgcn_s_setprio(0);
 #endif
-        if (ballot(bad && lane < K1)) { failed = true; fail_need = 0xFFFFFFF5u; break; }
+        if (ballot(bad && lane < K1)) { failed = true; fail_need = kFailCode; break; }
         BVG_T1(7, tq7);
         const uint32_t tq8 = BVG_T0();
         // ---- which lists are STORED: those that a later node copies from -- referenced inside the super-row (every reference of the
@@ -683,7 +683,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
             efirst = sk_run + eincl - cntE;
             sk_run += lane_get(eincl, 63);
         }
-        if (sk_run > sk_n) { failed = true; fail_need = 0xFFFFFFF5u; break; }   // index out of step with the stream
+        if (sk_run > sk_n) { failed = true; fail_need = kFailCode; break; }     // index out of step with the stream
         BVG_T1(8, tq8);
         BVG_T1(5, tq5);
 
@@ -703,7 +703,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
                 failed = true;
                 uint32_t d0 = lane_get(d, sa); const uint32_t n0 = lane_get(nres, sa);
                 if (d0 <= 0x3FFFFFFFu) d0 += (n0 > d0 ? d0 : n0) + 1u;
-                fail_need = d0 > 0x3FFFFFFFu ? 0xFFFFFFF2u : d0 + pool_used + (d0 >> 2) + 64;
+                fail_need = d0 > 0x3FFFFFFFu ? kFailHuge : d0 + pool_used + (d0 >> 2) + 64;
                 break;
             }
             cnt_sub++;
@@ -862,7 +862,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
                 }
             }
             blk_chk += csum;
-            if (ballot(bad)) { failed = true; fail_need = 0xFFFFFFF5u; break; }
+            if (ballot(bad)) { failed = true; fail_need = kFailCode; break; }
             wave_sync();
             BVG_T1(9, tq9);
             BVG_T1(5, tq8b);
@@ -1291,7 +1291,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
                 }
             }
             blk_chk += wsum;
-            if (ballot(wwbad)) { failed = true; fail_need = 0xFFFFFFF5u; break; }
+            if (ballot(wwbad)) { failed = true; fail_need = kFailCode; break; }
             // ---------------- leaf pass: the run queue, cut into chunks of kChunk elements dealt to all lanes.  Every referenced list
             // is complete by now.  A chunk is straight-line work: 4 elements per step, their LDS reads issued together.
             const uint32_t tqL = BVG_T0();

@@ -138,7 +138,7 @@ __global__ void __launch_bounds__(64, OCC) flat_kernel(DecodeArgs a) {
     uint64_t blk_arcs = 0, blk_chk = 0, blk_nodes = 0;
     unsigned err = 0;
     bool failed = false;
-    uint32_t fail_need = 0xFFFFFFFFu;
+    uint32_t fail_need = kFailUnknown;
     const uint64_t sk_base = a.skip_first[bid];
     const uint32_t sk_n = (uint32_t)(a.skip_first[bid + 1] - sk_base);
     uint32_t sk_run = 0;
@@ -217,7 +217,7 @@ __global__ void __launch_bounds__(64, OCC) flat_kernel(DecodeArgs a) {
             const bool inwin = valid && o1 + 96 <= stg_bit0 + stg_bits && o0 >= stg_bit0;
             uint32_t kg;
             { const uint64_t m = ballot(inwin); kg = m == ~0ull ? 64u : (uint32_t)__ffsll((unsigned long long)~m) - 1u; if (kg > nv) kg = nv; }
-            if (kg == 0) { if (g == 0) { failed = true; fail_need = 0xFFFFFFF1u; } break; }    // a single record larger than the window
+            if (kg == 0) { if (g == 0) { failed = true; fail_need = kFailWindow; } break; }    // a single record larger than the window
             // The records behind a round that the window cut short are the next super-row's first ones, and which of THIS super-row's last W lists
             // they copy from decides what is stored: their first 12 bytes are fetched now and looked at after the parse (their offsets are at hand).
             if (kg < nv && W > 0) {
@@ -263,7 +263,7 @@ __global__ void __launch_bounds__(64, OCC) flat_kernel(DecodeArgs a) {
                 const uint32_t bincl = wave_incl_scan32(bc > SCRH ? SCRH + 1 : bc);
                 const uint32_t kb = (uint32_t)__popcll(ballot(scr_used + bincl <= SCRH));
                 if (kb < kg) kg = kb;
-                if (kg == 0) { if (g == 0) { failed = true; fail_need = 0xFFFFFFF3u; } break; }
+                if (kg == 0) { if (g == 0) { failed = true; fail_need = kFailBlocks; } break; }
                 sb = CAP - scr_used - bincl;
                 scr_used += lane_get(bincl, kg - 1);
             }
@@ -304,7 +304,7 @@ __global__ void __launch_bounds__(64, OCC) flat_kernel(DecodeArgs a) {
                 const uint32_t iincl = wave_incl_scan32(iw > SCRH ? SCRH + 1 : iw);
                 const uint32_t ki = (uint32_t)__popcll(ballot(scr_used + iincl <= SCRH));
                 if (ki < kg) kg = ki;
-                if (kg == 0) { if (g == 0) { failed = true; fail_need = 0xFFFFFFF4u; } break; }
+                if (kg == 0) { if (g == 0) { failed = true; fail_need = kFailIntervals; } break; }
                 ib = CAP - scr_used - iincl;
                 scr_used += lane_get(iincl, kg - 1);
             }
@@ -331,7 +331,7 @@ __global__ void __launch_bounds__(64, OCC) flat_kernel(DecodeArgs a) {
                 }
                 nres = (uint32_t)extra;
             }
-            if (ballot(bad && lane < kg)) { failed = true; fail_need = 0xFFFFFFF5u; break; }
+            if (ballot(bad && lane < kg)) { failed = true; fail_need = kFailCode; break; }
             // the table entries of the round; then the marks: a record that copies says so on the list it copies from
             const bool rep = needed && lane < kg && x >= rep_lo && x < rep_hi;
             const uint32_t cntE = (parse && nres >= kSkipMin) ? (nres - 1u) >> kSkipShift : 0u;
@@ -345,7 +345,7 @@ __global__ void __launch_bounds__(64, OCC) flat_kernel(DecodeArgs a) {
                     tb.ref[r] = (uint8_t)ref; tb.fl[r] = (uint8_t)((needed ? F_NEED : 0u) | (rep ? F_REP : 0u)); tb.st[r] = 0;
                 }
             }
-            if (sk_run > sk_n || sk_n > 0xFFFFu) { failed = true; fail_need = 0xFFFFFFF5u; break; }   // index out of step with the stream
+            if (sk_run > sk_n || sk_n > 0xFFFFu) { failed = true; fail_need = kFailCode; break; }     // index out of step with the stream
             wave_sync();
             if (parse && ref > 0) atomicOr(reinterpret_cast<unsigned*>(tb.fl - wc) + (((int)r - (int)ref + (int)wc) >> 2), F_MARK << ((((int)r - (int)ref + (int)wc) & 3) * 8));
             if (rep) {                                                          // what the node adds besides k1 * (its successors): d * (k1 * base + k0)
@@ -483,7 +483,7 @@ __global__ void __launch_bounds__(64, OCC) flat_kernel(DecodeArgs a) {
                 uint32_t sm = 0;
                 for (uint32_t c = sa; c < se; c += 64) { const uint32_t j = c + lane; if (j < se && tb.st[j] > sm) sm = tb.st[j]; }
                 smax = wave_max32(sm);
-                if (smax > kMaxStage) { failed = true; fail_need = 0xFFFFFFF5u; break; }
+                if (smax > kMaxStage) { failed = true; fail_need = kFailCode; break; }
             }
 
             FT1(3, tqs);
@@ -573,7 +573,7 @@ __global__ void __launch_bounds__(64, OCC) flat_kernel(DecodeArgs a) {
                     FT1(5, tqc);
                 }
                 blk_chk += csum;
-                if (ballot(tbad)) { failed = true; fail_need = 0xFFFFFFF5u; break; }
+                if (ballot(tbad)) { failed = true; fail_need = kFailCode; break; }
                 wave_sync();
             }
 

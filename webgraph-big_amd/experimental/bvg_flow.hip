@@ -38,6 +38,10 @@ constexpr uint32_t kFlowRes = 32768;                    // residual values per b
 constexpr uint32_t kFlowMaxList = 8192;                 // longest list held (scratch-backed)
 constexpr uint32_t kFlowAux = 1024;                     // LDS words: stream window (stage 1) | copy blocks, intervals, insertion ranks (stage 2)
 constexpr uint32_t kAuxBlk = 256, kAuxIv = 128, kAuxC = kFlowAux - 2 * (kAuxBlk + kAuxIv);   // (two payload buffers)
+// fail_need reasons of this kernel only, beyond the shared kFail* (bvg_kernels.h)
+constexpr uint32_t kFailNodes = 0xFFFFFFF6u;            // more than kFlowNodes nodes in the block
+constexpr uint32_t kFailRing = 0xFFFFFFF7u;             // the list ring is full
+constexpr uint32_t kFailAux = 0xFFFFFFF8u;              // the aux area overflows
 
 struct Hdr { uint32_t d, pk, nres, boff, ioff, roff, flags, pad; };   // pk = ref | ic << 8 | bc << 16; flags: 1 needed, 2 reported, 4 some later node copies from it
 static_assert(sizeof(Hdr) == 32, "Hdr");
@@ -83,10 +87,10 @@ __global__ void __launch_bounds__(64, 5) flow_kernel(DecodeArgs a, uint32_t nwor
         uint64_t blk_arcs = 0, blk_chk = 0, blk_nodes = 0;
         unsigned err = 0;
         bool failed = false;
-        uint32_t fail_need = 0xFFFFFFF5u;
+        uint32_t fail_need = kFailCode;
         wave_sync();
         for (unsigned i = lane; i < (unsigned)kRing; i += 64) { nd_base[i] = 0; nd_d[i] = 0; }
-        if ((uint64_t)(e - hs) > kFlowNodes) { failed = true; fail_need = 0xFFFFFFF6u; }
+        if ((uint64_t)(e - hs) > kFlowNodes) { failed = true; fail_need = kFailNodes; }
 
         // residual skip index of this block
         const bool sk_have = a.skip_first != nullptr && (!a.skip_fmt || a.skip_fmt[bid] == 1);
@@ -131,7 +135,7 @@ __global__ void __launch_bounds__(64, 5) flow_kernel(DecodeArgs a, uint32_t nwor
                 k = m == ~0ull ? 64u : (uint32_t)__ffsll((unsigned long long)~m) - 1u;
                 if (k > left) k = left;
             }
-            if (k == 0) { failed = true; fail_need = 0xFFFFFFF1u; break; }
+            if (k == 0) { failed = true; fail_need = kFailWindow; break; }
             uint32_t rel = (uint32_t)(off_x - stg_bit0);
             const uint32_t pend = (uint32_t)(rec_end - stg_bit0);
             const uint32_t recrel = rel;
@@ -169,7 +173,7 @@ __global__ void __launch_bounds__(64, 5) flow_kernel(DecodeArgs a, uint32_t nwor
             //  separate partial-line stores per instruction)
             const uint32_t bincl = wave_incl_scan32(bc);
             const uint32_t sbl = bincl - bc, sb = boff_run + sbl;
-            if (boff_run + lane_get(bincl, 63) > kFlowBlk || lane_get(bincl, 63) > ring_cap) { failed = true; fail_need = 0xFFFFFFF3u; break; }
+            if (boff_run + lane_get(bincl, 63) > kFlowBlk || lane_get(bincl, 63) > ring_cap) { failed = true; fail_need = kFailBlocks; break; }
             bool malf = false;
             if (parse && !bad) {
                 if (ref > 0) {
@@ -196,7 +200,7 @@ __global__ void __launch_bounds__(64, 5) flow_kernel(DecodeArgs a, uint32_t nwor
             const uint32_t btot = lane_get(bincl, 63);
             const uint32_t iincl = wave_incl_scan32(2 * ic);
             const uint32_t ibl = btot + iincl - 2 * ic, ib = boff_run + ibl;
-            if (boff_run + btot + lane_get(iincl, 63) > kFlowBlk || btot + lane_get(iincl, 63) > ring_cap) { failed = true; fail_need = 0xFFFFFFF3u; break; }
+            if (boff_run + btot + lane_get(iincl, 63) > kFlowBlk || btot + lane_get(iincl, 63) > ring_cap) { failed = true; fail_need = kFailBlocks; break; }
             const bool rep = mine && x >= rep_lo && x < rep_hi;
             uint32_t k0 = 0, k1 = 0;
             if (rep) {
@@ -228,8 +232,8 @@ __global__ void __launch_bounds__(64, 5) flow_kernel(DecodeArgs a, uint32_t nwor
             // residual values: offsets in the scratch area
             const uint32_t rincl = wave_incl_scan32(nres);
             const uint32_t rb = roff_run + rincl - nres;
-            if (roff_run + lane_get(rincl, 63) > kFlowRes) { failed = true; fail_need = 0xFFFFFFF4u; break; }
-            if (ballot(malf)) { failed = true; fail_need = 0xFFFFFFF5u; break; }
+            if (roff_run + lane_get(rincl, 63) > kFlowRes) { failed = true; fail_need = kFailIntervals; break; }
+            if (ballot(malf)) { failed = true; fail_need = kFailCode; break; }
             // which lists does a later node of this block copy from?  (inside the row: ballots; earlier rows: a flag in their header)
             uint64_t refmask = 0;
             for (uint32_t r = 1; r <= W && r < 64; r++) refmask |= ballot(parse && ref == r) >> r;
@@ -323,8 +327,8 @@ __global__ void __launch_bounds__(64, 5) flow_kernel(DecodeArgs a, uint32_t nwor
                 wave_sync();
                 c0 = c1;
             }
-            if (rfail) { failed = true; fail_need = 0xFFFFFFF8u; break; }
-            if (ballot(bad && lane < k)) { failed = true; fail_need = d > kFlowMaxList ? d + (d >> 2) + 64u : 0xFFFFFFF5u; break; }
+            if (rfail) { failed = true; fail_need = kFailAux; break; }
+            if (ballot(bad && lane < k)) { failed = true; fail_need = d > kFlowMaxList ? d + (d >> 2) + 64u : kFailCode; break; }
             blk_chk += chk;
             {   // headers of the row: LDS -> scratch area, coalesced (8 words per node, nodes are consecutive)
                 if (lane < k && in_range) {
@@ -432,7 +436,7 @@ __global__ void __launch_bounds__(64, 5) flow_kernel(DecodeArgs a, uint32_t nwor
                                 ring_used = lane_get(nincl, 63);
                                 wave_sync();
                             }
-                            if (ring_used + d > ring_cap) { failed = true; fail_need = 0xFFFFFFF7u; break; }
+                            if (ring_used + d > ring_cap) { failed = true; fail_need = kFailRing; break; }
                             ob = ring_used; ring_used += d;
                         } else {                                                  // a long list: scratch-backed, circular
                             if (gl_used + d > gl_cap) gl_used = 0;
@@ -477,7 +481,7 @@ __global__ void __launch_bounds__(64, 5) flow_kernel(DecodeArgs a, uint32_t nwor
                         }
                     } else {
                         const bool tailkeep = !(bc & 1u);
-                        if (stored && nres > kAuxC) { failed = true; fail_need = 0xFFFFFFF8u; break; }
+                        if (stored && nres > kAuxC) { failed = true; fail_need = kFailAux; break; }
                         // ---- every residual: where does it fall in the referenced list?  (equal heads -> literal tier; insertion ranks kept for stored lists)
                         for (uint32_t j0 = 0; j0 < nres; j0 += 64) {
                             const uint32_t jj = j0 + lane; const bool on = jj < nres;
@@ -541,7 +545,7 @@ __global__ void __launch_bounds__(64, 5) flow_kernel(DecodeArgs a, uint32_t nwor
                     wave_sync();
                 }
             }
-            if (ballot(zbad)) { failed = true; fail_need = 0xFFFFFFF5u; }
+            if (ballot(zbad)) { failed = true; fail_need = kFailCode; }
             blk_chk += chk;
         }
 

@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(64 * NW) rows_wg_kernel(DecodeArgs a) {
     uint64_t blk_arcs = 0, blk_chk = 0, blk_nodes = 0;        // per wavefront
     unsigned err = 0;
     bool failed = false;
-    uint32_t fail_need = 0xFFFFFFFFu;
+    uint32_t fail_need = kFailUnknown;
 
     const bool sk_have = a.skip_first != nullptr && (!a.skip_fmt || a.skip_fmt[bid] == 1);
     const uint64_t sk_base = sk_have ? a.skip_first[bid] : 0ull;
@@ -106,7 +106,7 @@ __global__ void __launch_bounds__(64 * NW) rows_wg_kernel(DecodeArgs a) {
             kwin = m == ~0ull ? 64u : (uint32_t)__ffsll((unsigned long long)~m) - 1u;
             if (kwin > left) kwin = left;
         }
-        if (kwin == 0) { failed = true; fail_need = 0xFFFFFFF1u; break; }      // a single record larger than the window
+        if (kwin == 0) { failed = true; fail_need = kFailWindow; break; }      // a single record larger than the window
         uint32_t rel = (uint32_t)(off_x - stg_bit0);
         const uint32_t pend = (uint32_t)(rec_end - stg_bit0);
         const uint32_t recrel = rel;
@@ -172,7 +172,7 @@ __global__ void __launch_bounds__(64 * NW) rows_wg_kernel(DecodeArgs a) {
             }
             const uint32_t bincl = wave_incl_scan32(bc > SCR ? SCR + 1 : bc);
             { const uint32_t kb = (uint32_t)__popcll(ballot(bincl <= SCR)); k = kb < k ? kb : k; }
-            if (k == 0) { kfail = 0xFFFFFFF3u; k = 1; }                       // one node's copy blocks exceed the scratch area
+            if (k == 0) { kfail = kFailBlocks; k = 1; }                       // one node's copy blocks exceed the scratch area
             sb = bincl - bc;
             uint32_t btot = lane_get(bincl, k - 1);
             if (parse0 && lane < k && !kfail) {
@@ -205,7 +205,7 @@ __global__ void __launch_bounds__(64 * NW) rows_wg_kernel(DecodeArgs a) {
                 if (ki != 0 || k <= 1) { k = ki < k ? ki : k; break; }
                 k = (k + 1u) >> 1; btot = lane_get(bincl, k - 1);
             }
-            if (k == 0) { kfail = 0xFFFFFFF4u; k = 1; }                       // one node's intervals exceed the scratch area
+            if (k == 0) { kfail = kFailIntervals; k = 1; }                    // one node's intervals exceed the scratch area
             ib = btot + iincl - iw;
             if (parse0 && lane < k && !kfail) {
                 if (ic > 0) {                                                 // intervals, BVG:1042-1058
@@ -267,7 +267,7 @@ __global__ void __launch_bounds__(64 * NW) rows_wg_kernel(DecodeArgs a) {
             failed = true;
             uint32_t d0 = lane_get(d, 0); const uint32_t n0 = lane_get(nres, 0);
             if (d0 <= 0x3FFFFFFFu) d0 += (n0 > d0 ? d0 : n0) + 1u;
-            fail_need = d0 > 0x3FFFFFFFu ? 0xFFFFFFF2u : d0 + pool_used + (d0 >> 2) + 64;
+            fail_need = d0 > 0x3FFFFFFFu ? kFailHuge : d0 + pool_used + (d0 >> 2) + 64;
             break;
         }
         const bool act = needed && lane < k;
@@ -279,7 +279,7 @@ __global__ void __launch_bounds__(64 * NW) rows_wg_kernel(DecodeArgs a) {
             const int64_t nx = r0 + k + lane;
             if (nx < e) { nxt_off = a.offsets[nx]; nxt_end = a.offsets[nx + 1]; }
         }
-        if (ballot(bad && lane < k)) { failed = true; fail_need = 0xFFFFFFF5u; break; }
+        if (ballot(bad && lane < k)) { failed = true; fail_need = kFailCode; break; }
 
         // ------------------------------------------------------------------ phase 1b: residuals, one task per <= 32-gap segment
         bool lbad = false;
@@ -292,7 +292,7 @@ __global__ void __launch_bounds__(64 * NW) rows_wg_kernel(DecodeArgs a) {
                 const uint32_t eincl = wave_incl_scan32(cE);
                 efirst = sk_run + eincl - cE;
                 sk_run += lane_get(eincl, 63);
-                if (sk_run > sk_n) { failed = true; fail_need = 0xFFFFFFF5u; break; }      // index out of step with the stream
+                if (sk_run > sk_n) { failed = true; fail_need = kFailCode; break; }        // index out of step with the stream
             }
             const uint32_t Tn = hasres ? 1u + cntE : 0u;
             const uint32_t tincl = wave_incl_scan32(Tn), ts = tincl - Tn, Ttot = lane_get(tincl, 63);
@@ -336,7 +336,7 @@ __global__ void __launch_bounds__(64 * NW) rows_wg_kernel(DecodeArgs a) {
             if (wv == 0 && ((act && d == 0) || (parse && nres == 0)) && rel != pend) err |= ERR_MALFORMED;   // SURVEY A.6 self-check
         }
         if (act && wv == 0) pool[rtb + nres] = sentinel<T>();                // guard behind the node's residual positions
-        if (ballot(lbad || malf) && lane == 0) wg_flags = 0xFFFFFFF5u;
+        if (ballot(lbad || malf) && lane == 0) wg_flags = kFailCode;
         __syncthreads();
         {
             const uint32_t fl = wg_flags;
@@ -508,7 +508,7 @@ __global__ void __launch_bounds__(64 * NW) rows_wg_kernel(DecodeArgs a) {
                     }
                     wave_sync();
                 }
-                if (ballot(zbad) && lane == 0) wg_flags = 0xFFFFFFF5u;
+                if (ballot(zbad) && lane == 0) wg_flags = kFailCode;
                 __syncthreads();                                              // the level's lists are complete
             }
             {

@@ -420,8 +420,7 @@ __global__ void __launch_bounds__(64) stream_kernel(DecodeArgs a) {
 void launch_stream_decode(const DecodeArgs& a, uint32_t nblocks, bool wide, bool materialise, hipStream_t s) {
     if (nblocks == 0) return;
     dim3 grid(nblocks), block(64);
-    const bool gen = !(a.cod.outdegree == BVG_GAMMA && a.cod.reference == BVG_UNARY && a.cod.block_count == BVG_GAMMA &&
-                       a.cod.block == BVG_GAMMA && a.cod.residual == BVG_ZETA);
+    const bool gen = !is_default_codings(a.cod);
     const size_t dyn = (size_t)a.lds_pool_elems * (wide ? 8 : 4);
 #define BVG_SL(T, M) do { if (gen) hipLaunchKernelGGL((stream_kernel<T, M, true>), grid, block, dyn, s, a); \
                           else hipLaunchKernelGGL((stream_kernel<T, M, false>), grid, block, dyn, s, a); } while (0)
