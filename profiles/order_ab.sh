@@ -1,7 +1,7 @@
 #!/bin/bash
 # launch order / stream priority of the big-list tiers vs tier 0 at the full 8 GiB size
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-run() { python bench.py --steps 5 --warmup 3 --no-cpu-baseline ${ARGS} 2>/dev/null | python3 -c "
+run() { python bench.py --steps 5 --warmup 3 --full --no-cpu-baseline ${ARGS} 2>/dev/null | python3 -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{\"metric'):

@@ -2,7 +2,7 @@
 # skip-index granularity: edges/s and index bytes per scan for library builds with different (kSkipMin, kSkipEvery)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 for lib in ${LIBS:-libbvgraph_hip.so}; do for sh in eu web w0; do
-  BVG_HIP_LIB=$PWD/webgraph-big_amd/lib/$lib python bench.py --shape $sh --steps 3 --warmup 2 --target-gib 2 --no-cpu-baseline 2>/dev/null | python3 -c "
+  BVG_HIP_LIB=$PWD/webgraph-big_amd/lib/$lib python bench.py --shape $sh --steps 3 --warmup 2 --target-gib 2 --full --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{\"metric'):
