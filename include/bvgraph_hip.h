@@ -205,6 +205,19 @@ int bvg_transpose_dev(bvg_graph* g, void* d_toffsets, void* d_tsucc, uint64_t ts
 int bvg_symmetrize(bvg_graph* g, uint64_t* soffsets, int64_t* ssucc, uint64_t ssucc_cap, uint64_t* n_arcs);
 int bvg_symmetrize_dev(bvg_graph* g, void* d_soffsets, void* d_ssucc, uint64_t ssucc_cap, uint64_t* n_arcs);
 
+/* ---- weakly connected components (algo/ConnectedComponents.java) ----
+ * comp[nodes]: the weak component of every node, numbered as ConnectedComponents.compute numbers them on a symmetric graph
+ * (ParallelBreadthFirstVisit.visitAll, ParallelBreadthFirstVisit.java:272-337): component c is the one whose smallest node is the
+ * c-th smallest among the components' smallest nodes.  Arcs are taken in both directions, so a directed graph gives its weak
+ * components (= compute(new UnionImmutableGraph(g, gT)), the reference's `main -t`) without a transpose.  A concurrent union-find over
+ * one parent element per node (4 bytes; 8 on the 64-bit kernels) consumes the decode one arc-bounded batch at a time: the graph never
+ * has to fit in HBM as a CSR.  sizes (may be NULL) = computeSizes(): sizes[c] = nodes of component c; *n_components = their number.
+ * sizes_cap below the count: BVG_E_CAPACITY, *n_components and comp written all the same.  Requires node_base == 0.  Malformed
+ * streams report the decode's status (a successor outside [0, nodes): BVG_E_EOF).  _dev: comp / sizes in device memory (int64). */
+#define BVG_CC_SORT_BY_SIZE 1u   /* ConnectedComponents.sortBySize: components renumbered by decreasing size, ties by smallest node */
+int bvg_components(bvg_graph* g, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components);
+int bvg_components_dev(bvg_graph* g, uint32_t flags, void* d_comp, void* d_sizes, uint64_t sizes_cap, uint64_t* n_components);
+
 /* ---- arc labels stored as a bit stream (labelling/BitStreamArcLabelledImmutableGraph.java) ----
  * basename.labels holds, node after node, the labels of the node's arcs in successor order (:75-84); basename.labeloffsets the
  * gamma-coded bit lengths of those runs after a leading gamma(0) (store(), :655-680).  The node iterator reads `outdegree`

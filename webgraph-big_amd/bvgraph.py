@@ -153,6 +153,20 @@ def lib():
     return _LIB
 
 
+def _components_fns():
+    """bvg_components / bvg_components_dev, bound on first use: a build of the library without them (the host emulator's) still loads."""
+    L = lib()
+    if getattr(L, "_cc_bound", False):
+        return L
+    vp, u64 = C.c_void_p, C.c_uint64
+    for name in ("bvg_components", "bvg_components_dev"):
+        if not hasattr(L, name):
+            raise UnsupportedOperationException(_abi.E_UNSUPPORTED, name + " is not in this build of the library")
+        getattr(L, name).argtypes = [vp, C.c_uint32, vp, vp, u64, C.POINTER(u64)]
+    L._cc_bound = True
+    return L
+
+
 def store(adj, params=None, chunk_nodes=0, device=0):
     """BVGraph.store on the device (bvg_store): adj = (adj_off uint64[n+1], succ int64[m]) or a list of sorted lists.
     Returns (graph uint8[], offsets uint64[n+1]); byte for byte what the reference's compressor writes."""
@@ -728,6 +742,45 @@ class BVGraph:
         _check(st, "symmetrize")
         return soff, ssucc[:int(need.value)]
 
+    def connected_components(self, sizes=False, sort_by_size=False):
+        """ConnectedComponents (algo/ConnectedComponents.java) of the graph with its arcs taken in both directions -- the weak
+        components; on a symmetric graph exactly compute(g).component -- by a union-find on the device (bvg_components).
+        Component c is the one whose smallest node is the c-th smallest among the components' smallest nodes; sort_by_size=True
+        renumbers by decreasing size, ties by smallest node (sortBySize).  sizes=True also returns computeSizes()."""
+        L = _components_fns()
+        n = self.num_nodes()
+        comp = np.empty(max(n, 1), dtype=np.int64)
+        cnt = C.c_uint64(0)
+        flags = CC_SORT_BY_SIZE if sort_by_size else 0
+        sz = None
+        cap = max(n, 1) if sizes else 0
+        if sizes:
+            sz = np.empty(cap, dtype=np.int64)
+        _check(L.bvg_components(self._h, flags, comp.ctypes.data, None if sz is None else sz.ctypes.data, cap, C.byref(cnt)), "connected_components")
+        k = int(cnt.value)
+        return ComponentsResult(k, comp[:n], None if sz is None else sz[:k])
+
+    connectedComponents = connected_components
+
+    def connected_components_dev(self, comp_tensor, sizes_tensor=None, sort_by_size=False):
+        """bvg_components_dev: labels into comp_tensor (int64, numNodes() elements, on the graph's device) and, when given, sizes
+        into sizes_tensor (int64; BVG_E_CAPACITY -> IllegalArgumentException if it holds fewer than the count).  Returns the count."""
+        import torch
+        L = _components_fns()
+        n = self.num_nodes()
+        for t, what in ((comp_tensor, "comp"), (sizes_tensor, "sizes")):
+            if t is not None and (not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous()):
+                raise IllegalArgumentException(_abi.E_ARG, "%s must be a contiguous int64 CUDA tensor" % what)
+        if comp_tensor.numel() < n:
+            raise IllegalArgumentException(_abi.E_ARG, "comp holds %d elements, the graph %d nodes" % (comp_tensor.numel(), n))
+        cnt = C.c_uint64(0)
+        st = L.bvg_components_dev(self._h, CC_SORT_BY_SIZE if sort_by_size else 0, comp_tensor.data_ptr() if n else None,
+                                  None if sizes_tensor is None else sizes_tensor.data_ptr(), 0 if sizes_tensor is None else sizes_tensor.numel(), C.byref(cnt))
+        if st == _abi.E_CAPACITY:
+            raise IllegalArgumentException(st, "connected_components_dev: %d components, sizes holds %d" % (int(cnt.value), sizes_tensor.numel()))
+        _check(st, "connected_components_dev")
+        return int(cnt.value)
+
     def build_index(self, frm=0, to=None):
         """Builds the residual skip index (and validates the blocks) of nodes [frm, to) now (bvg_build_index) instead of inside
         the first scan; returns (entries, bytes) of the graph's index afterwards."""
@@ -755,6 +808,67 @@ class BVGraph:
 
 
 BALANCE_NODES, BALANCE_BITS, BALANCE_ARCS = 0, 1, 2
+CC_SORT_BY_SIZE = 1
+
+
+class ComponentsResult:
+    """What ConnectedComponents holds after compute(): numberOfComponents (count), component[] (int64 per node) and, when asked
+    for, computeSizes() (sizes, int64 per component; None otherwise)."""
+
+    def __init__(self, count, component, sizes=None):
+        self.count, self.component, self.sizes = int(count), component, sizes
+
+    numberOfComponents = property(lambda self: self.count)
+
+    def __repr__(self):
+        return "ComponentsResult(count=%d, nodes=%d, sizes=%s)" % (self.count, len(self.component), "yes" if self.sizes is not None else "no")
+
+
+def store_components(result, results_basename):
+    """ConnectedComponents.main's output files: results_basename.wcc = the component of every node and, when the result has sizes,
+    results_basename.wccsizes = the size of every component, each as BinIO.storeLongs writes them (big-endian int64, no header).
+    Returns the paths written."""
+    paths = [results_basename + ".wcc"]
+    np.asarray(result.component, dtype=">i8").tofile(paths[0])
+    if result.sizes is not None:
+        paths.append(results_basename + ".wccsizes")
+        np.asarray(result.sizes, dtype=">i8").tofile(paths[1])
+    return paths
+
+
+def load_components(results_basename):
+    """Reads back what store_components wrote (BinIO.loadLongs): (component, sizes or None) as native int64 arrays."""
+    comp = np.fromfile(results_basename + ".wcc", dtype=">i8").astype(np.int64)
+    sp = results_basename + ".wccsizes"
+    sizes = np.fromfile(sp, dtype=">i8").astype(np.int64) if os.path.exists(sp) else None
+    return comp, sizes
+
+
+def components_arg_parser():
+    """The command line of ConnectedComponents.main: basename [resultsBasename], -s/--sizes, -r/--renumber (the weak components
+    of the graph are computed directly: no symmetric graph and no -t transpose are needed)."""
+    import argparse
+    ap = argparse.ArgumentParser(prog="components", description="Weakly connected components of a BVGraph, computed on the device.")
+    ap.add_argument("-s", "--sizes", action="store_true", help="also store the component sizes (resultsBasename.wccsizes)")
+    ap.add_argument("-r", "--renumber", action="store_true", help="renumber components by decreasing size (ties: smallest node first)")
+    ap.add_argument("--device", type=int, default=0, help="the GPU to run on")
+    ap.add_argument("basename", help="the basename of the graph")
+    ap.add_argument("results_basename", nargs="?", default=None, help="the basename of the result files (default: the graph's basename)")
+    return ap
+
+
+def components_main(argv=None):
+    """ConnectedComponents.main: loads basename, computes the components, writes resultsBasename.wcc (and .wccsizes with -s)."""
+    args = components_arg_parser().parse_args(argv)
+    out = args.results_basename or args.basename
+    g = BVGraph.load(args.basename, device=args.device)
+    try:
+        r = g.connected_components(sizes=args.sizes, sort_by_size=args.renumber)
+    finally:
+        g.close()
+    store_components(r, out)
+    print("%d components" % r.count)
+    return r
 
 
 def mosaic(graphs, cycles):

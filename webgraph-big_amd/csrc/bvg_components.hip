@@ -1,0 +1,372 @@
+// bvg_components.hip — weakly connected components on the device (algo/ConnectedComponents.java).
+//
+// The reference runs ParallelBreadthFirstVisit.visitAll() over a symmetric graph (ParallelBreadthFirstVisit.java:272-337): nodes are
+// scanned in increasing order and a new round starts at every node not visited yet, so component c is the one whose smallest node is the
+// c-th smallest among the components' smallest nodes.  Here the same partition and the same numbering come from a concurrent union-find
+// over a parent array (one element per node) that consumes the decode one arc-bounded batch at a time: no transpose, no symmetric copy,
+// no CSR of the whole graph in HBM.  Union-find is symmetric, so hooking every arc of a directed graph gives its weak components
+// (= compute(new UnionImmutableGraph(g, gT)), the reference's `main -t`).
+//
+//   init      parent[x] = x
+//   hook      per arc (u, v) of a materialised batch: find both roots (path halving), link the larger root under the smaller with a
+//             compare-and-swap, retry from the value a failed CAS returns.  A root only ever gets a smaller parent, so every final root
+//             is the smallest node of its component: the reference's numbering with no extra pass.
+//   compress  parent[x] = find(x) (a read-only walk); flag[x] = x is a root
+//   number    rank = exclusive scan of the flags; comp[x] = rank[parent[x]]; the count is the scan total
+//   sizes     histogram of comp, one atomic per run of equal labels inside a wavefront (the giant component makes one address hot)
+//   sort      ConnectedComponents.sortBySize: stable radix sort of (n - size, old index), the permutation inverted, comp remapped
+//
+// Concurrency.  parent[] is read and halved with plain loads and stores: a CU's vector L1 is never refreshed by another CU's stores,
+// so a read may be stale, and the agent-scope CAS of a link is the authoritative re-read.  Values only ever move to ancestors
+// (parent[x] <= x always, and a halving store writes an ancestor of x), so a stale read is an older ancestor: it costs a longer walk
+// or a failed CAS, never a wrong partition, and every retry moves to a smaller id, so none spins.  (Agent-scope atomic loads, which
+// bypass L1, made the hook 1.7 times slower on the eu-like stand-in: DESIGN.md.)  A CAS succeeds only on a root, and a halving store touches only a node that is no root any more, so the two never
+// overwrite each other's link.  Roots are read with loads first and the CAS is issued only when they differ: at most n - 1 CASes
+// succeed, so the atomic count scales with nodes, not arcs.
+#include <cstdint>
+#include <cstring>
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "bvg_host.h"
+#include "../../include/bvgraph_hip.h"
+
+namespace bvg {
+
+namespace {
+
+// plain loads and stores (L1-cached): a stale value is an older ancestor, and the CAS in unite() is the authoritative re-read
+template <typename T> __device__ __forceinline__ T ld_parent(const T* p) { return *p; }
+template <typename T> __device__ __forceinline__ void st_parent(T* p, T v) { *p = v; }
+
+// root of x with path halving: parent[x] <- parent[parent[x]] on the way up (benign races: both values are ancestors of x).
+// HALVE = false: a read-only walk (compress: there a halving store could overwrite a node's root, just written by its own thread,
+// with an ancestor further down)
+template <typename T, bool HALVE = true> __device__ __forceinline__ T find_root_from(T* parent, T x, T p) {   // (p: parent[x] as read)
+    while (p != x) {
+        const T gp = ld_parent(parent + p);
+        if (gp == p) return p;
+        if (HALVE) st_parent(parent + x, gp);
+        x = gp;
+        p = ld_parent(parent + x);
+    }
+    return x;
+}
+template <typename T, bool HALVE = true> __device__ __forceinline__ T find_root(T* parent, T x) { return find_root_from<T, HALVE>(parent, x, ld_parent(parent + x)); }
+
+// union of the trees of roots a and b (any order): the larger root goes under the smaller.  A failed CAS returns the value that
+// took its place (the authoritative re-read): the larger root has been linked meanwhile, so both roots are looked up again.
+template <typename T> __device__ __forceinline__ void unite(T* parent, T a, T b) {
+    while (a != b) {
+        const T hi = a > b ? a : b, lo = a > b ? b : a;
+        T expect = hi;
+        if (__hip_atomic_compare_exchange_strong(parent + hi, &expect, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+        a = find_root(parent, expect);
+        b = find_root(parent, lo);
+    }
+}
+
+// Every kernel strides over its elements: a launch holds fewer than 2^32 work-items, and graphs may have more nodes than that.
+#define CC_FOR(I, N) for (int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; I < (int64_t)(N); I += (int64_t)gridDim.x * blockDim.x)
+
+template <typename T> __global__ void cc_init_kernel(T* parent, int64_t n) {
+    CC_FOR(x, n) parent[x] = (T)x;
+}
+
+// One wavefront per 64 consecutive nodes of the batch [lo, lo + cnt) (four per workgroup): the root of every source is found once per
+// list (LDS), then the lanes walk the 64 lists' arcs in chunks of 64 -- the owner of arc t is the number of list ends <= t, as in
+// expand_sources_kernel (bvg_transpose.hip) -- find the target's root and unite when the roots differ.  A target outside [0, n) is a
+// malformed stream: it is flagged (*bad) and not followed.
+template <typename T> __global__ void __launch_bounds__(256) cc_hook_kernel(const uint64_t* cum, int64_t lo, int64_t cnt, const int64_t* succ, int64_t n,
+                                                                            T* parent, unsigned* bad) {
+    __shared__ uint64_t ends_s[4][64];
+    __shared__ T root_s[4][64];
+    const unsigned w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int64_t x0 = ((int64_t)blockIdx.x * 4 + w) * 64; x0 < cnt; x0 += (int64_t)gridDim.x * 256) {   // (whole wavefronts: no workgroup barrier)
+    const int64_t xe = x0 + 64 < cnt ? x0 + 64 : cnt;
+    const int c = (int)(xe - x0);
+    uint64_t* ends = ends_s[w]; T* roots = root_s[w];
+    const uint64_t a0 = cum[x0], a1 = cum[xe];
+    if ((int)lane < c) {
+        const uint64_t e = cum[x0 + lane + 1];
+        ends[lane] = e;
+        roots[lane] = e > cum[x0 + lane] ? find_root(parent, (T)(lo + x0 + lane)) : (T)0;   // (no arcs: never read)
+    }
+    __builtin_amdgcn_wave_barrier();                                    // (LDS operations of one wavefront complete in order)
+    bool oob = false;
+    for (uint64_t t = a0 + lane; t < a1; t += 64) {
+        int l = 0, r = c;
+        while (l < r) { const int m = (l + r) >> 1; if (ends[m] <= t) l = m + 1; else r = m; }
+        const int64_t y = succ[t];
+        if (y < 0 || y >= n) { oob = true; continue; }
+        const T ru = roots[l];
+        const T pv = ld_parent(parent + y);
+        if (pv == ru) continue;                                         // (the common case once the source's component is hooked: one load)
+        const T rv = find_root_from(parent, (T)y, pv);
+        if (ru != rv) unite(parent, ru, rv);
+    }
+    if (oob) atomicOr(bad, 1u);
+    __builtin_amdgcn_wave_barrier();                                    // (the next group's LDS writes after every lane's reads)
+    }
+}
+
+// parent[x] = root of x; flag[x] = 1 for the roots.  Only thread x writes parent[x], and with the root, so the label kernel reads
+// every node's root in one load; the other threads' walks through x see the old or the new value, both ancestors
+template <typename T> __global__ void cc_compress_kernel(T* parent, int64_t n, int32_t* flag) {
+    CC_FOR(x, n) {
+        const T r = find_root<T, false>(parent, (T)x);
+        st_parent(parent + x, r);
+        flag[x] = r == (T)x ? 1 : 0;
+    }
+}
+
+template <typename T> __global__ void cc_label_kernel(const T* parent, int64_t n, const uint64_t* rank, int64_t* comp) {
+    CC_FOR(x, n) comp[x] = (int64_t)rank[parent[x]];
+}
+
+// sizes[comp[x]] += 1: consecutive nodes mostly share a label, so each wavefront adds one count per run of equal labels among its
+// 64 lanes (atomics run at the memory side: 64 lanes on one hot address would serialise there)
+__global__ void __launch_bounds__(256) cc_sizes_kernel(const int64_t* comp, int64_t n, unsigned long long* sizes) {
+    const unsigned lane = threadIdx.x & 63;
+    for (int64_t x0 = (int64_t)blockIdx.x * blockDim.x; x0 < n; x0 += (int64_t)gridDim.x * blockDim.x) {   // (uniform per workgroup: ballots below)
+    const int64_t x = x0 + threadIdx.x;
+    const bool in = x < n;
+    const int64_t c = in ? comp[x] : -1;
+    const int64_t prev = __shfl_up(c, 1, 64);
+    const bool head = in && (lane == 0 || prev != c);
+    const uint64_t heads = __ballot(head);
+    const uint64_t live = __ballot(in);
+    if (head) {
+        const uint64_t above = lane == 63 ? 0ull : heads & (~0ull << (lane + 1));
+        const unsigned next = above ? (unsigned)__builtin_ctzll(above) : 64u - (unsigned)__builtin_clzll(live);   // (live: the low lanes)
+        atomicAdd(sizes + c, (unsigned long long)(next - lane));
+    }
+    }
+}
+
+// sort key of component i: n - size (ascending = size descending); values: the old index (increasing, so a stable sort orders ties by it)
+__global__ void cc_sort_keys_kernel(const unsigned long long* sizes, uint64_t count, uint64_t n, uint64_t* keys, uint64_t* idx) {
+    CC_FOR(i, count) {
+        keys[i] = n - (uint64_t)sizes[i];
+        idx[i] = (uint64_t)i;
+    }
+}
+
+// new index of old component order[j] is j; sizes in the new order
+__global__ void cc_invert_kernel(const uint64_t* keys_sorted, const uint64_t* order, uint64_t count, uint64_t n, uint64_t* newidx, unsigned long long* sizes) {
+    CC_FOR(j, count) {
+        newidx[order[j]] = (uint64_t)j;
+        sizes[j] = (unsigned long long)(n - keys_sorted[j]);
+    }
+}
+
+__global__ void cc_remap_kernel(int64_t* comp, int64_t n, const uint64_t* newidx) {
+    CC_FOR(x, n) comp[x] = (int64_t)newidx[comp[x]];
+}
+
+// per batch bound j: the prefix sum at the bound and at the node before it (the arcs of a segment without its last list)
+__global__ void cc_gather_bounds_kernel(const uint64_t* cum, const uint64_t* first, uint64_t nb, uint64_t* at, uint64_t* before) {
+    CC_FOR(j, nb + 1) {
+        const uint64_t b = first[j];
+        at[j] = cum[b];
+        before[j] = b ? cum[b - 1] : 0;
+    }
+}
+
+inline unsigned grid(int64_t n, int64_t per) { const int64_t b = (n + per - 1) / per; return (unsigned)(b < 1 ? 1 : (b > (1 << 18) ? (1 << 18) : b)); }   // (the kernels stride)
+
+}  // namespace
+
+}  // namespace bvg
+
+namespace {
+
+using bvghost::DevBuf;
+
+constexpr uint64_t kMaxBatchArcs = 1ull << 32;     // 32 GiB of successors: the per-batch overhead (a plan lookup, two syncs) is already negligible
+
+constexpr int64_t kMaxBatchNodes = 1ll << 30;      // node ranges of a launch stay well below 2^32 work-items
+
+struct Batch { int64_t lo, hi; uint64_t arcs; };
+
+// outdegrees of [from, to) into out[0, to - from): launch_outdegrees runs one work-item per node, so longer ranges go in pieces
+void outdegrees_of(bvg_graph* g, int64_t from, int64_t to, int32_t* out) {
+    Shared* sh = g->sh;
+    for (int64_t a = from; a < to; a += kMaxBatchNodes)
+        launch_outdegrees(sh->d_graph, sh->nbytes, sh->offs, a, std::min(to, a + kMaxBatchNodes), sh->p.outdegree_coding, out + (a - from), nullptr, g->stream);
+}
+
+// [0, n) cut into node ranges of at most `per` arcs each, except that a list longer than that forms a batch on its own.  The whole
+// graph's outdegrees and their prefix sums are computed on the device; the cut points are the lower bounds of j * per in the prefix
+// sums (launch_plan_boundaries), so a segment holds < per arcs before its last list and is split before that list when the whole
+// exceeds per.
+int plan_batches(bvg_graph* g, uint64_t per, std::vector<Batch>& out, uint64_t* arcs_out, uint64_t* longest_out) {
+    Shared* sh = g->sh; const int64_t n = sh->p.nodes;
+    DevBuf deg, cum, tmp;
+    if (deg.alloc((size_t)n * 4) || cum.alloc(((size_t)n + 1) * 8) || tmp.alloc(scan_tmp_elems(n) * 8)) return BVG_E_NOMEM;
+    outdegrees_of(g, 0, n, (int32_t*)deg.p);
+    launch_exclusive_scan((const int32_t*)deg.p, (uint64_t*)cum.p, n, (uint64_t*)tmp.p, g->stream);
+    uint64_t arcs = 0;
+    HIPCHK(hipMemcpyAsync(&arcs, (uint64_t*)cum.p + n, 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    *arcs_out = arcs; *longest_out = 0;
+    out.clear();
+    if (arcs == 0) return 0;
+    if (per == 0) per = 1;
+    const uint64_t nb = (arcs + per - 1) / per;
+    DevBuf first, at, before;
+    if (first.alloc((nb + 1) * 8) || at.alloc((nb + 1) * 8) || before.alloc((nb + 1) * 8)) return BVG_E_NOMEM;
+    launch_plan_boundaries(Offsets{nullptr, nullptr, (const uint64_t*)cum.p}, n, per, nb, (uint64_t*)first.p, g->stream);
+    hipLaunchKernelGGL(cc_gather_bounds_kernel, dim3(grid((int64_t)nb + 1, 256)), dim3(256), 0, g->stream, (const uint64_t*)cum.p, (const uint64_t*)first.p, nb,
+                       (uint64_t*)at.p, (uint64_t*)before.p);
+    std::vector<uint64_t> hf(nb + 1), ha(nb + 1), hb(nb + 1);
+    HIPCHK(hipMemcpyAsync(hf.data(), first.p, (nb + 1) * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(ha.data(), at.p, (nb + 1) * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(hb.data(), before.p, (nb + 1) * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    for (uint64_t j = 0; j < nb; j++) {
+        const uint64_t b0 = hf[j], b1 = hf[j + 1];
+        if (b1 <= b0) continue;
+        const uint64_t all = ha[j + 1] - ha[j], last = ha[j + 1] - hb[j + 1];     // arcs of the segment, of its last list
+        if (all <= per || b1 - b0 == 1) out.push_back(Batch{(int64_t)b0, (int64_t)b1, all});
+        else { out.push_back(Batch{(int64_t)b0, (int64_t)b1 - 1, all - last}); out.push_back(Batch{(int64_t)b1 - 1, (int64_t)b1, last}); }
+    }
+    std::vector<Batch> cut;                                                  // (and at most kMaxBatchNodes nodes each: runs of empty lists)
+    for (const Batch& b : out) {
+        if (b.hi - b.lo <= kMaxBatchNodes) { cut.push_back(b); continue; }
+        for (int64_t a = b.lo; a < b.hi; a += kMaxBatchNodes) cut.push_back(Batch{a, std::min(b.hi, a + kMaxBatchNodes), b.arcs});   // (arcs: a bound)
+    }
+    out.swap(cut);
+    for (const Batch& b : out) if (b.arcs > *longest_out) *longest_out = b.arcs;
+    return 0;
+}
+
+template <typename T> int components_t(bvg_graph* g, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components, bool dev) {
+    Shared* sh = g->sh; const int64_t n = sh->p.nodes;
+    const bool dbgt = dbg_on();
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const auto tA = now();
+    // the residual skip index first, for the whole graph (a no-op when it exists): batches below a quarter of the graph would not build
+    // it and would all run on the checking kernels.  A build that fails leaves the batches index-less, nothing worse.
+    if (g->tun.no_index != 1 && n >= 4096) (void)bvg_build_index(g, 0, n, nullptr, nullptr);
+    DevBuf parent;
+    if (parent.alloc((size_t)n * sizeof(T))) return BVG_E_NOMEM;
+    T* const d_parent = (T*)parent.p;
+    hipLaunchKernelGGL((cc_init_kernel<T>), dim3(grid(n, 256)), dim3(256), 0, g->stream, d_parent, n);
+    // batch budget: half of what is free once the parent array is there, less headroom for the decode's own workspaces; at most kMaxBatchArcs
+    uint64_t per = 0;
+    if (const char* k = knob("BVG_CC_BATCH_ARCS")) { const long long v = atoll(k); if (v > 0) per = (uint64_t)v; }
+    if (!per) {
+        size_t fr = 0, tot = 0;
+        HIPCHK(hipMemGetInfo(&fr, &tot));
+        const uint64_t head = (256ull << 20) + fr / 16 + (uint64_t)n * 12;            // (+ the node-side arrays of a batch and the planning pass)
+        per = fr > head ? (fr - head) / 2 / 8 : 1;
+        if (per > kMaxBatchArcs) per = kMaxBatchArcs;
+        if (per < 1) per = 1;
+    }
+    std::vector<Batch> batches; uint64_t arcs = 0, longest = 0;
+    int rc = plan_batches(g, per, batches, &arcs, &longest); if (rc) return rc;
+    const auto tB = now();
+    double t_dec = 0, t_hook = 0;
+    DevBuf d_bad;
+    if (d_bad.alloc(256)) return BVG_E_NOMEM;
+    HIPCHK(hipMemsetAsync(d_bad.p, 0, sizeof(unsigned), g->stream));
+    if (!batches.empty()) {
+        int64_t maxn = 0; for (const Batch& b : batches) maxn = std::max(maxn, b.hi - b.lo);
+        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t o_cum = 0, o_tmp = o_cum + al(((size_t)maxn + 1) * 8), o_deg = o_tmp + al(scan_tmp_elems(maxn) * 8), o_succ = o_deg + al((size_t)maxn * 4);
+        DevBuf ws;
+        if (ws.alloc(o_succ + (size_t)std::max<uint64_t>(longest, 1) * 8)) return BVG_E_NOMEM;   // parent array + the largest batch: does not fit
+        char* const w = (char*)ws.p;
+        uint64_t* const b_cum = (uint64_t*)(w + o_cum); int32_t* const b_deg = (int32_t*)(w + o_deg); int64_t* const b_succ = (int64_t*)(w + o_succ);
+        for (const Batch& b : batches) {
+            const int64_t cnt = b.hi - b.lo;
+            const auto t0 = now();
+            outdegrees_of(g, b.lo, b.hi, b_deg);
+            launch_exclusive_scan(b_deg, b_cum, cnt, (uint64_t*)(w + o_tmp), g->stream);
+            rc = run_decode(g, b.lo, b.hi, true, b_cum, b_succ, nullptr, nullptr); if (rc) return rc;
+            if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); }
+            const auto t1 = now();
+            hipLaunchKernelGGL((cc_hook_kernel<T>), dim3(grid(cnt, 256)), dim3(256), 0, g->stream, (const uint64_t*)b_cum, b.lo, cnt, (const int64_t*)b_succ, n, d_parent,
+                               (unsigned*)d_bad.p);
+            HIPCHK(hipGetLastError());
+            if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); t_dec += ms(t0, t1); t_hook += ms(t1, now()); }
+        }
+    }
+    unsigned bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, d_bad.p, sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    if (bad) return BVG_E_EOF;                                              // a successor outside [0, n): malformed stream
+    const auto tC = now();
+    // compress + number (the batch buffer is gone by now)
+    DevBuf flag, rank, tmp, dcomp;
+    if (flag.alloc((size_t)n * 4) || rank.alloc(((size_t)n + 1) * 8) || tmp.alloc(scan_tmp_elems(n) * 8)) return BVG_E_NOMEM;
+    int64_t* d_comp = comp;
+    if (!dev) { if (dcomp.alloc((size_t)n * 8)) return BVG_E_NOMEM; d_comp = (int64_t*)dcomp.p; }
+    hipLaunchKernelGGL((cc_compress_kernel<T>), dim3(grid(n, 256)), dim3(256), 0, g->stream, d_parent, n, (int32_t*)flag.p);
+    launch_exclusive_scan((const int32_t*)flag.p, (uint64_t*)rank.p, n, (uint64_t*)tmp.p, g->stream);
+    hipLaunchKernelGGL((cc_label_kernel<T>), dim3(grid(n, 256)), dim3(256), 0, g->stream, (const T*)d_parent, n, (const uint64_t*)rank.p, d_comp);
+    uint64_t count = 0;
+    HIPCHK(hipMemcpyAsync(&count, (uint64_t*)rank.p + n, 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    if (n_components) *n_components = count;
+    const bool want_sizes = sizes != nullptr || (flags & BVG_CC_SORT_BY_SIZE);
+    const bool cap_ok = sizes == nullptr || sizes_cap >= count;
+    if (want_sizes && count) {
+        DevBuf dsz;
+        unsigned long long* d_sizes = (dev && sizes && cap_ok) ? (unsigned long long*)sizes : nullptr;
+        if (!d_sizes) { if (dsz.alloc(count * 8)) return BVG_E_NOMEM; d_sizes = (unsigned long long*)dsz.p; }
+        HIPCHK(hipMemsetAsync(d_sizes, 0, count * 8, g->stream));
+        hipLaunchKernelGGL(cc_sizes_kernel, dim3(grid(n, 256)), dim3(256), 0, g->stream, (const int64_t*)d_comp, n, d_sizes);
+        if (flags & BVG_CC_SORT_BY_SIZE) {
+            const unsigned bits = 64u - (unsigned)__builtin_clzll((unsigned long long)n);       // keys n - size <= n - 1
+            size_t sort_b = 0;
+            if (rocprim::radix_sort_pairs(nullptr, sort_b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)count, 0u, bits, g->stream) != hipSuccess)
+                return BVG_E_HIP;
+            DevBuf keys, keys2, idx, idx2, st;                               // (idx2 doubles as the inverse permutation)
+            if (keys.alloc(count * 8) || keys2.alloc(count * 8) || idx.alloc(count * 8) || idx2.alloc(count * 8) || st.alloc(sort_b)) return BVG_E_NOMEM;
+            hipLaunchKernelGGL(cc_sort_keys_kernel, dim3(grid((int64_t)count, 256)), dim3(256), 0, g->stream, (const unsigned long long*)d_sizes, count, (uint64_t)n,
+                               (uint64_t*)keys.p, (uint64_t*)idx.p);
+            if (rocprim::radix_sort_pairs(st.p, sort_b, (const uint64_t*)keys.p, (uint64_t*)keys2.p, (const uint64_t*)idx.p, (uint64_t*)idx2.p, (size_t)count, 0u, bits, g->stream) != hipSuccess)
+                return BVG_E_HIP;
+            hipLaunchKernelGGL(cc_invert_kernel, dim3(grid((int64_t)count, 256)), dim3(256), 0, g->stream, (const uint64_t*)keys2.p, (const uint64_t*)idx2.p, count, (uint64_t)n,
+                               (uint64_t*)idx.p, d_sizes);
+            hipLaunchKernelGGL(cc_remap_kernel, dim3(grid(n, 256)), dim3(256), 0, g->stream, d_comp, n, (const uint64_t*)idx.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(g->stream));
+        }
+        if (sizes && cap_ok) {
+            if (!dev) HIPCHK(hipMemcpyAsync(sizes, d_sizes, count * 8, hipMemcpyDeviceToHost, g->stream));
+            else if ((void*)d_sizes != (void*)sizes) HIPCHK(hipMemcpyAsync(sizes, d_sizes, count * 8, hipMemcpyDeviceToDevice, g->stream));
+        }
+        HIPCHK(hipStreamSynchronize(g->stream));
+    }
+    if (!dev) HIPCHK(hipMemcpy(comp, d_comp, (size_t)n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipGetLastError());
+    const auto tD = now();
+    if (dbgt) fprintf(stderr, "[bvg] components: plan %.1f ms (%zu batches of <= %llu arcs, %llu arcs), decode %.1f ms, hook %.1f ms, finish %.1f ms (%llu components)\n",
+                      ms(tA, tB), batches.size(), (unsigned long long)per, (unsigned long long)arcs, t_dec, t_hook, ms(tC, tD), (unsigned long long)count);
+    return cap_ok ? 0 : BVG_E_CAPACITY;
+}
+
+int components_impl(bvg_graph* g, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components, bool dev) {
+    if (!g) return BVG_E_ARG;
+    if (flags & ~(uint32_t)BVG_CC_SORT_BY_SIZE) return BVG_E_ARG;
+    if (g->node_base != 0) return BVG_E_ARG;                 // a shard's targets leave its node range: the whole graph only
+    Shared* sh = g->sh;
+    if (n_components) *n_components = 0;
+    if (sh->p.nodes == 0) return 0;
+    if (!comp) return BVG_E_ARG;
+    HIPCHK(hipSetDevice(sh->device));
+    const bool wide = sh->wide || g->tun.force_wide;
+    return wide ? components_t<uint64_t>(g, flags, comp, sizes, sizes_cap, n_components, dev) : components_t<uint32_t>(g, flags, comp, sizes, sizes_cap, n_components, dev);
+}
+
+}  // namespace
+
+int bvg_components(bvg_graph* g, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components) {
+    return guarded([&] { return components_impl(g, flags, comp, sizes, sizes_cap, n_components, false); });
+}
+int bvg_components_dev(bvg_graph* g, uint32_t flags, void* d_comp, void* d_sizes, uint64_t sizes_cap, uint64_t* n_components) {
+    return guarded([&] { return components_impl(g, flags, (int64_t*)d_comp, (int64_t*)d_sizes, sizes_cap, n_components, true); });
+}

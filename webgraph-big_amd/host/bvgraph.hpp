@@ -166,6 +166,18 @@ public:
         ssucc.resize((size_t)need);
         if (need) check(bvg_symmetrize(h_, soffsets.data(), ssucc.data(), need, &need), "symmetrize");
     }
+    // weakly connected components (ConnectedComponents.compute + computeSizes / sortBySize, algo/ConnectedComponents.java) by a
+    // union-find on the device: comp[x] for every node, sizes per component when asked for; returns the number of components
+    int64_t connectedComponents(std::vector<int64_t>& comp, std::vector<int64_t>* sizes = nullptr, bool sortBySize = false) {
+        const size_t n = (size_t)p_.nodes;
+        comp.resize(n);
+        if (sizes) sizes->resize(n ? n : 1);                                                // (there are at most n components)
+        uint64_t count = 0;
+        check(bvg_components(h_, sortBySize ? BVG_CC_SORT_BY_SIZE : 0u, n ? comp.data() : nullptr, sizes ? sizes->data() : nullptr, sizes ? (uint64_t)sizes->size() : 0,
+                             &count), "components");
+        if (sizes) sizes->resize((size_t)count);
+        return (int64_t)count;
+    }
     NodeIterator nodeIterator(int64_t from = 0) { return NodeIterator(shared_from_this(), from, INT64_MAX); }   // BVGraph.java:1257
     std::vector<NodeIterator> splitNodeIterators(int howMany) {                            // ImmutableGraph.java:405-436
         std::vector<NodeIterator> v; const int64_t n = p_.nodes, m = (n + howMany - 1) / howMany;
