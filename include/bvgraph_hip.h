@@ -139,7 +139,7 @@ int bvg_decode_range_dev(bvg_graph* g, int64_t from, int64_t to, void* d_outdeg,
 void* bvg_host_alloc(size_t bytes);
 void bvg_host_free(void* p);
 /* successors(x) for a whole frontier at once (BVG:860-867 per element; the access pattern of
- * algo/ParallelBreadthFirstVisit.java and algo/HyperBall.java:774-822): nodes[count] in any order, repeats
+ * algo/ParallelBreadthFirstVisit.java -- bvg_bfs_visit below runs it without leaving the device -- and algo/HyperBall.java:774-822): nodes[count] in any order, repeats
  * allowed; outdeg[count] and the successor lists concatenated in request order.  Each request is
  * decoded together with the few earlier nodes its reference chain reaches (the recursion of BVG:1084). */
 int bvg_successors_batch(bvg_graph* g, const int64_t* nodes, int64_t count, int32_t* outdeg, int64_t* succ, uint64_t succ_cap, uint64_t* n_succ);
@@ -217,6 +217,43 @@ int bvg_symmetrize_dev(bvg_graph* g, void* d_soffsets, void* d_ssucc, uint64_t s
 #define BVG_CC_SORT_BY_SIZE 1u   /* ConnectedComponents.sortBySize: components renumbered by decreasing size, ties by smallest node */
 int bvg_components(bvg_graph* g, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components);
 int bvg_components_dev(bvg_graph* g, uint32_t flags, void* d_comp, void* d_sizes, uint64_t sizes_cap, uint64_t* n_components);
+
+/* ---- breadth-first visits (algo/ParallelBreadthFirstVisit.java) ----
+ * A visit object keeps on the device what the reference's class keeps (ParallelBreadthFirstVisit.java:79-148): marker[nodes] (-1 = not
+ * enqueued yet; otherwise the round in which the node was reached, or its parent with BVG_BFS_PARENT), the round counter (-1 before the
+ * first visit), the queue of the last visit and its cut points -- level d is queue[cut[d] .. cut[d + 1]), the last cut point is the queue
+ * size, maxDistance() = n_cutpoints - 2, nodeAtMaxDistance() = the last queue element -- plus dist[nodes] (int32): the level of every node
+ * of the queue, -1 for every other node.  It holds a bvg_copy() flyweight of g (own stream and workspaces), so g stays usable from
+ * another thread and may be closed first.  Requires node_base == 0 (BVG_E_ARG).  One object is not re-entrant.
+ * DETERMINISM, where the reference depends on thread timing (:183, :188-190): inside each level the queue holds the nodes in INCREASING
+ * ID; with BVG_BFS_PARENT the parent of a node is the SMALLEST node of the previous level that has it as a successor, the root's parent
+ * is itself.
+ * bvg_bfs_clear: every marker and the round back to -1 (:141-147); the queue, the cut points and dist are forgotten too.
+ * bvg_bfs_visit: visit(start) (:222-266).  A start that is marked already: *visited = 0 and nothing changes, not even the queue.  Otherwise
+ * the round is incremented, queue and cut points are replaced, *visited = the queue size.  Start outside [0, nodes): BVG_E_ARG.
+ * bvg_bfs_visit_all: visitAll() (:272-339): clear, then one visit per node that is still unmarked, in increasing node order, each with its
+ * own round.  As in the reference (:309-317) a node with no successors, or whose only successor is itself, gets its marker and its round
+ * but does not replace queue and cut points: afterwards they (and dist) are those of the last visit that had something to expand.  On a
+ * symmetric graph the round markers are the component numbers of bvg_components.
+ * bvg_bfs_get / _get_dev (device buffers): any pointer may be NULL; marker, queue (int64) and cutpoints (uint64) as sized by bvg_bfs_info,
+ * dist int32[nodes]; a capacity below the size is BVG_E_CAPACITY and nothing is written.
+ * Malformed streams report the decode's status (a successor outside [0, nodes): BVG_E_EOF, never used as an index).  After an error the
+ * object is in the cleared state.  Each level is expanded by random access to the frontier's lists or, when the frontier is large, by a
+ * sequential decode of the whole graph in arc-bounded batches; bvg_bfs_counters reports what ran: out[BVG_BFS_COUNTERS] =
+ * levels on the frontier route, levels on the sweep route, requests decoded through the block plan ("deep"), frontier batches, sweep
+ * batches, levels whose queue segment was sorted, levels compacted from the node range, route of the last visit's first level (1 / 2). */
+#define BVG_BFS_PARENT 1u
+#define BVG_BFS_COUNTERS 8
+typedef struct bvg_bfs bvg_bfs;
+int bvg_bfs_create(bvg_graph* g, uint32_t flags, bvg_bfs** out);
+void bvg_bfs_close(bvg_bfs* v);
+int bvg_bfs_clear(bvg_bfs* v);
+int bvg_bfs_visit(bvg_bfs* v, int64_t start, uint64_t* visited);
+int bvg_bfs_visit_all(bvg_bfs* v);
+int bvg_bfs_info(const bvg_bfs* v, int64_t* round, uint64_t* queue_size, uint64_t* n_cutpoints);
+int bvg_bfs_get(bvg_bfs* v, int64_t* marker, int64_t* queue, uint64_t queue_cap, uint64_t* cutpoints, uint64_t cut_cap, int32_t* dist);
+int bvg_bfs_get_dev(bvg_bfs* v, void* d_marker, void* d_queue, uint64_t queue_cap, void* d_cutpoints, uint64_t cut_cap, void* d_dist);
+int bvg_bfs_counters(const bvg_bfs* v, uint64_t* out);
 
 /* ---- arc labels stored as a bit stream (labelling/BitStreamArcLabelledImmutableGraph.java) ----
  * basename.labels holds, node after node, the labels of the node's arcs in successor order (:75-84); basename.labeloffsets the

@@ -38,6 +38,17 @@ class Tuning(C.Structure):
 DELTA, GAMMA, GOLOMB, SKEWED_GOLOMB, UNARY, ZETA, NIBBLE = 1, 2, 3, 4, 5, 6, 7
 LOAD_OFFLINE, LOAD_SEQUENTIAL, LOAD_STANDARD, LOAD_MAPPED = -1, 0, 1, 2
 
+# bvg_bfs_create flags / the number of words bvg_bfs_counters writes (BVG_BFS_PARENT, BVG_BFS_COUNTERS)
+BFS_PARENT_FLAG, BFS_COUNTER_WORDS = 1, 8
+
+
+def bfs_signatures():
+    """argtypes of the bvg_bfs_* entry points (breadth-first visits), by name."""
+    vp, i64, u64, pp = C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(C.c_void_p)
+    return {"bvg_bfs_create": [vp, C.c_uint32, pp], "bvg_bfs_close": [vp], "bvg_bfs_clear": [vp], "bvg_bfs_visit": [vp, i64, C.POINTER(u64)],
+            "bvg_bfs_visit_all": [vp], "bvg_bfs_info": [vp, C.POINTER(i64), C.POINTER(u64), C.POINTER(u64)],
+            "bvg_bfs_get": [vp, vp, vp, u64, vp, u64, vp], "bvg_bfs_get_dev": [vp, vp, vp, u64, vp, u64, vp], "bvg_bfs_counters": [vp, vp]}
+
 OK, E_ARG, E_STATE, E_UNSUPPORTED, E_IO, E_EOF, E_NOMEM, E_HIP, E_CAPACITY = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 

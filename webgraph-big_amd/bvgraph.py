@@ -167,6 +167,21 @@ def _components_fns():
     return L
 
 
+def _bfs_fns():
+    """The bvg_bfs_* entry points, bound on first use (as _components_fns: a build of the library without them still loads)."""
+    L = lib()
+    if getattr(L, "_bfs_bound", False):
+        return L
+    sigs = _abi.bfs_signatures()
+    for name, args in sigs.items():
+        if not hasattr(L, name):
+            raise UnsupportedOperationException(_abi.E_UNSUPPORTED, name + " is not in this build of the library")
+        getattr(L, name).argtypes = args
+    L.bvg_bfs_close.restype = None
+    L._bfs_bound = True
+    return L
+
+
 def store(adj, params=None, chunk_nodes=0, device=0):
     """BVGraph.store on the device (bvg_store): adj = (adj_off uint64[n+1], succ int64[m]) or a list of sorted lists.
     Returns (graph uint8[], offsets uint64[n+1]); byte for byte what the reference's compressor writes."""
@@ -781,6 +796,12 @@ class BVGraph:
         _check(st, "connected_components_dev")
         return int(cnt.value)
 
+    def breadth_first_visit(self, parent=False):
+        """ParallelBreadthFirstVisit (algo/ParallelBreadthFirstVisit.java) with its state on the device: see BreadthFirstVisit."""
+        return BreadthFirstVisit(self, parent)
+
+    breadthFirstVisit = breadth_first_visit
+
     def build_index(self, frm=0, to=None):
         """Builds the residual skip index (and validates the blocks) of nodes [frm, to) now (bvg_build_index) instead of inside
         the first scan; returns (entries, bytes) of the graph's index afterwards."""
@@ -809,6 +830,120 @@ class BVGraph:
 
 BALANCE_NODES, BALANCE_BITS, BALANCE_ARCS = 0, 1, 2
 CC_SORT_BY_SIZE = 1
+BFS_PARENT = 1
+BFS_COUNTERS = ("frontier_levels", "sweep_levels", "deep_requests", "frontier_batches", "sweep_batches", "sorted_levels", "compacted_levels", "first_level_route")
+
+
+class BreadthFirstVisit:
+    """What ParallelBreadthFirstVisit holds (marker, round, queue, cutPoints; ParallelBreadthFirstVisit.java:79-148), kept on the device
+    between visits (bvg_bfs_*), plus dist: the level of every node of the last visit, -1 for the others.  Where the reference depends
+    on thread timing this is fixed: inside a level the queue is in increasing id, and with parent=True marker[x] is the smallest node
+    of the previous level that has x as a successor (the root's parent is itself); otherwise marker[x] is the round that reached x.
+    The object holds its own flyweight of the graph.  Usable as a context manager."""
+
+    def __init__(self, graph, parent=False):
+        self._L = _bfs_fns()
+        self._v = C.c_void_p()
+        self._n = graph.num_nodes()
+        self.parent = bool(parent)
+        _check(self._L.bvg_bfs_create(graph._h, BFS_PARENT if parent else 0, C.byref(self._v)), "breadth_first_visit")
+
+    def close(self):
+        if getattr(self, "_v", None):
+            self._L.bvg_bfs_close(self._v)
+            self._v = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self):
+        _check(self._L.bvg_bfs_clear(self._v), "clear")
+
+    def visit(self, start):
+        """visit(start): the number of nodes visited (0 when start was marked already: nothing changes then)."""
+        k = C.c_uint64(0)
+        _check(self._L.bvg_bfs_visit(self._v, start, C.byref(k)), "visit(%d)" % start)
+        return int(k.value)
+
+    def visit_all(self):
+        _check(self._L.bvg_bfs_visit_all(self._v), "visit_all")
+
+    visitAll = visit_all
+
+    def _info(self):
+        r, q, c = C.c_int64(), C.c_uint64(), C.c_uint64()
+        _check(self._L.bvg_bfs_info(self._v, C.byref(r), C.byref(q), C.byref(c)), "info")
+        return int(r.value), int(q.value), int(c.value)
+
+    @property
+    def round(self):
+        return self._info()[0]
+
+    @property
+    def queue(self):
+        q = self._info()[1]
+        out = np.empty(q, dtype=np.int64)
+        if q:
+            _check(self._L.bvg_bfs_get(self._v, None, out.ctypes.data, q, None, 0, None), "queue")
+        return out
+
+    @property
+    def cut_points(self):
+        c = self._info()[2]
+        out = np.empty(c, dtype=np.uint64)
+        if c:
+            _check(self._L.bvg_bfs_get(self._v, None, None, 0, out.ctypes.data, c, None), "cut_points")
+        return out.astype(np.int64)
+
+    cutPoints = cut_points
+
+    @property
+    def marker(self):
+        out = np.empty(self._n, dtype=np.int64)
+        if self._n:
+            _check(self._L.bvg_bfs_get(self._v, out.ctypes.data, None, 0, None, 0, None), "marker")
+        return out
+
+    @property
+    def dist(self):
+        out = np.empty(self._n, dtype=np.int32)
+        if self._n:
+            _check(self._L.bvg_bfs_get(self._v, None, None, 0, None, 0, out.ctypes.data), "dist")
+        return out
+
+    def get_dev(self, marker=None, queue=None, cut_points=None, dist=None):
+        """bvg_bfs_get_dev into contiguous CUDA tensors (marker, queue, cut_points: int64; dist: int32) on the graph's device."""
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _check(self._L.bvg_bfs_get_dev(self._v, ptr(marker), ptr(queue), 0 if queue is None else queue.numel(), ptr(cut_points),
+                                       0 if cut_points is None else cut_points.numel(), ptr(dist)), "get_dev")
+
+    def max_distance(self):
+        """maxDistance(): cutPoints.size() - 2 (ParallelBreadthFirstVisit.java:355-357)."""
+        return self._info()[2] - 2
+
+    def node_at_max_distance(self):
+        """nodeAtMaxDistance(): the last element of the queue (:346-348)."""
+        q = self.queue
+        if not len(q):
+            raise IndexError("node_at_max_distance: the queue is empty")
+        return int(q[-1])
+
+    maxDistance, nodeAtMaxDistance = max_distance, node_at_max_distance
+
+    def counters(self):
+        """What ran since the object was made (bvg_bfs_counters): levels per route, batches, requests decoded through the block plan, ..."""
+        out = np.zeros(len(BFS_COUNTERS), dtype=np.uint64)
+        _check(self._L.bvg_bfs_counters(self._v, out.ctypes.data), "counters")
+        return dict(zip(BFS_COUNTERS, (int(x) for x in out)))
 
 
 class ComponentsResult:

@@ -8,6 +8,176 @@
 // There is no CPU decode path in this library.
 #include "bvg_host.h"
 
+namespace bvghost {
+
+// Per-handle device workspace for the materialising calls: grown on demand, kept between calls (a NodeIterator asks for batch
+// after batch of the same size; a fresh hipMalloc / hipFree pair per buffer and call cost more than the decode of a small batch).
+static int dr_ensure(bvg_graph* g, size_t bytes) {
+    if (bytes <= g->dr_ws_bytes) return 0;
+    if (g->dr_ws) { (void)hipFree(g->dr_ws); g->dr_ws = nullptr; g->dr_ws_bytes = 0; }
+    const size_t want = bytes + bytes / 4;
+    if (hipMalloc(&g->dr_ws, want) != hipSuccess) {
+        (void)hipGetLastError();
+        if (hipMalloc(&g->dr_ws, bytes) != hipSuccess) { (void)hipGetLastError(); g->dr_ws = nullptr; return BVG_E_NOMEM; }
+        g->dr_ws_bytes = bytes; return 0;
+    }
+    g->dr_ws_bytes = want;
+    return 0;
+}
+
+int decode_range_impl(bvg_graph* g, int64_t from, int64_t to, int32_t* outdeg, int64_t* succ, uint64_t cap, uint64_t* n_succ, bool dev, bool narrow) {
+    if (!g) return BVG_E_ARG;
+    Shared* sh = g->sh;
+    if (narrow && (dev || (uint64_t)sh->p.nodes + g->node_base > 0xFFFFFFFFull)) return BVG_E_UNSUPPORTED;   // 32-bit ids: host path, every id below 2^32 - 1 (0xFFFFFFFF stands for the -1 of a malformed stream, never for a node)
+    if (from < 0 || to > sh->p.nodes || from > to) return BVG_E_ARG;               // BVG:863,1000,1128
+    if (from == to) { if (n_succ) *n_succ = 0; return 0; }
+    HIPCHK(hipSetDevice(sh->device));
+    const int64_t cnt = to - from;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // workspace: [cum | scan tmp | deg (unless the caller's device buffer takes them)] and, for host callers, the successors behind them
+    const size_t o_cum = 0, o_tmp = o_cum + al(((size_t)cnt + 1) * sizeof(uint64_t)), o_deg = o_tmp + al(scan_tmp_elems(cnt) * sizeof(uint64_t));
+    const size_t o_succ = o_deg + al((size_t)cnt * sizeof(int32_t));
+    int rc = dr_ensure(g, o_succ); if (rc) return rc;
+    auto at = [&](size_t off) { return (char*)g->dr_ws + off; };
+    int32_t* d_deg = (dev && outdeg) ? outdeg : (int32_t*)at(o_deg);
+    uint64_t* d_cum = (uint64_t*)at(o_cum);
+    launch_outdegrees(sh->d_graph, sh->nbytes, sh->offs, from, to, sh->p.outdegree_coding, d_deg, nullptr, g->stream);
+    launch_exclusive_scan(d_deg, d_cum, cnt, (uint64_t*)at(o_tmp), g->stream);
+    uint64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, d_cum + cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    if (n_succ) *n_succ = total;
+    if (total > cap || (!succ && total > 0)) {          // query / too small: report the size (and the outdegrees)
+        if (outdeg && !dev) HIPCHK(hipMemcpy(outdeg, d_deg, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
+        return BVG_E_CAPACITY;
+    }
+    int64_t* d_succ = succ;
+    if (!dev) {
+        const size_t per = sizeof(int64_t) + (narrow ? sizeof(uint32_t) : 0);
+        if (o_succ + (size_t)(total ? total : 1) * per + 256 > g->dr_ws_bytes) {
+            // growing moves the workspace: the prefix sums are recomputed rather than copied (two tiny kernels)
+            rc = dr_ensure(g, o_succ + (size_t)(total ? total : 1) * per + 256); if (rc) return rc;
+            d_deg = (int32_t*)at(o_deg); d_cum = (uint64_t*)at(o_cum);
+            launch_outdegrees(sh->d_graph, sh->nbytes, sh->offs, from, to, sh->p.outdegree_coding, d_deg, nullptr, g->stream);
+            launch_exclusive_scan(d_deg, d_cum, cnt, (uint64_t*)at(o_tmp), g->stream);
+        }
+        d_succ = (int64_t*)at(o_succ);
+    }
+    rc = run_decode(g, from, to, true, d_cum, d_succ, d_deg, nullptr);
+    if (rc == 0 && !dev) {
+        // device -> host on the handle's stream: at PCIe rate when the caller's buffers are page-locked (bvg_host_alloc)
+        if (total && narrow) {
+            uint32_t* d32 = (uint32_t*)at(o_succ + al((size_t)total * sizeof(int64_t)));
+            launch_narrow_succ(d_succ, d32, total, g->stream);
+            HIPCHK(hipMemcpyAsync(succ, d32, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, g->stream));
+        } else if (total) HIPCHK(hipMemcpyAsync(succ, d_succ, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+        if (outdeg) HIPCHK(hipMemcpyAsync(outdeg, d_deg, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipStreamSynchronize(g->stream));
+    }
+    return rc;
+}
+
+// ---- bvg_successors_batch and the frontier route of bvg_bfs_visit: successors(x) for requests that are on the device already, the results staying there.
+// Three steps, so that a caller can size its buffers (or choose another way) once the arc count is known:
+//   batch_degrees  outdegrees of the requests, their prefix sums, the two plan entries {x, x + 1} per request; *total = the arcs
+//   batch_halos    the halo of every request (the earlier nodes its reference chain reaches).  A request whose chain reaches more than 64 nodes back
+//                  (possible with maxrefcount x window > 64) does not fit a request block's halo: it is taken out of the batch (an empty block) and
+//                  listed in `deep`, for the caller to decode through the graph's block plan, whose blocks are cut so that every chain fits
+//                  (successors(x) recurses as deep as the chain goes, BVG:1084): decode_range_impl(x, x + 1) into d_succ + deep[k].at
+//   batch_decode   the decode of the request blocks into d_succ (list i at cum[i])
+size_t batch_bufs_bytes(int64_t count) { return batch_bufs_at(nullptr, count).end; }
+BatchBufs batch_bufs_at(char* base, int64_t count) {
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t c = (size_t)(count > 0 ? count : 1);
+    size_t o = 0;
+    BatchBufs b{};
+    b.deg = (int32_t*)(base + o); o += al(c * sizeof(int32_t));
+    b.first = (uint64_t*)(base + o); o += al((2 * c + 1) * sizeof(uint64_t));
+    b.cum = (uint64_t*)(base + o); o += al((c + 1) * sizeof(uint64_t));
+    b.tmp = (uint64_t*)(base + o); o += al(scan_tmp_elems((int64_t)c) * sizeof(uint64_t));
+    b.halo = (uint32_t*)(base + o); o += al(2 * c * sizeof(uint32_t));
+    b.mask = (uint64_t*)(base + o); o += al(2 * c * sizeof(uint64_t));
+    b.deep = (uint64_t*)(base + o); o += al((3 * c + 1) * sizeof(uint64_t));
+    b.end = o;
+    return b;
+}
+int batch_degrees(bvg_graph* g, const BatchBufs& b, const int64_t* d_nodes, int64_t count, uint64_t* total) {
+    Shared* sh = g->sh;
+    launch_outdegrees_gather(sh->d_graph, sh->nbytes, sh->offs, d_nodes, count, sh->p.outdegree_coding, b.deg, b.first, g->stream);
+    launch_exclusive_scan(b.deg, b.cum, count, b.tmp, g->stream);
+    HIPCHK(hipMemcpyAsync(total, b.cum + count, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    return 0;
+}
+int batch_halos(bvg_graph* g, const BatchBufs& b, const int64_t* d_nodes, int64_t count, std::vector<DeepRequest>& deep) {
+    Shared* sh = g->sh;
+    deep.clear();
+    HIPCHK(hipMemsetAsync(b.deep, 0, sizeof(uint64_t), g->stream));
+    launch_plan_halo(sh->d_graph, sh->nbytes, sh->offs, sh->p.nodes, b.first, (uint32_t)(2 * count), sh->p.window_size, codings_of(sh->p), b.halo, b.mask, g->stream);
+    launch_batch_deep(d_nodes, count, b.cum, b.first, b.halo, b.deep, g->stream);
+    uint64_t nd = 0;
+    HIPCHK(hipMemcpyAsync(&nd, b.deep, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    if (nd) {                                                                // (few, if any: a host round trip for those alone)
+        std::vector<uint64_t> h(3 * (size_t)nd);
+        HIPCHK(hipMemcpy(h.data(), b.deep + 1, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        for (uint64_t k = 0; k < nd; k++) deep.push_back(DeepRequest{(int64_t)h[3 * k], h[3 * k + 1], h[3 * k + 2]});
+        std::sort(deep.begin(), deep.end(), [](const DeepRequest& x, const DeepRequest& y) { return x.index < y.index; });   // (the device lists them in any order)
+    }
+    return 0;
+}
+int batch_decode(bvg_graph* g, const BatchBufs& b, int64_t count, int64_t* d_succ) {
+    BatchPlan bp{b.first, b.halo, b.mask, (uint32_t)count};
+    return run_decode(g, 0, g->sh->p.nodes, true, b.cum, d_succ, nullptr, nullptr, &bp);
+}
+
+static int bvg_successors_batch_impl(bvg_graph* g, const int64_t* nodes, int64_t count, int32_t* outdeg, int64_t* succ, uint64_t succ_cap, uint64_t* n_succ) {
+    if (!g || (!nodes && count) || count < 0) return BVG_E_ARG;
+    Shared* sh = g->sh;
+    for (int64_t i = 0; i < count; i++) if (nodes[i] < 0 || nodes[i] >= sh->p.nodes) return BVG_E_ARG;      // BVG:863
+    if (n_succ) *n_succ = 0;
+    if (count == 0) return 0;
+    if (count > kMaxBatchRequests) return BVG_E_ARG;
+    HIPCHK(hipSetDevice(sh->device));
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t c = (size_t)count;
+    // workspace: [requests | the batch's node-side arrays | successors]
+    const size_t o_bufs = al(c * sizeof(int64_t)), o_succ = o_bufs + batch_bufs_bytes(count);
+    int rc = dr_ensure(g, o_succ); if (rc) return rc;
+    uint64_t total = 0;
+    std::vector<DeepRequest> deep;
+    BatchBufs b{};
+    auto prepare = [&]() -> int {
+        b = batch_bufs_at((char*)g->dr_ws + o_bufs, count);
+        HIPCHK(hipMemcpyAsync(g->dr_ws, nodes, c * sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
+        int r = batch_degrees(g, b, (const int64_t*)g->dr_ws, count, &total); if (r) return r;
+        return batch_halos(g, b, (const int64_t*)g->dr_ws, count, deep);
+    };
+    rc = prepare(); if (rc) return rc;
+    if (n_succ) *n_succ = total;
+    if (outdeg) HIPCHK(hipMemcpy(outdeg, b.deg, c * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (total > succ_cap || (!succ && total > 0)) return BVG_E_CAPACITY;
+    if (o_succ + (size_t)(total ? total : 1) * sizeof(int64_t) > g->dr_ws_bytes) {
+        rc = dr_ensure(g, o_succ + (size_t)(total ? total : 1) * sizeof(int64_t)); if (rc) return rc;
+        rc = prepare(); if (rc) return rc;                                   // the workspace moved: redo the (cheap) preparation in the new one
+    }
+    int64_t* const d_succ = (int64_t*)((char*)g->dr_ws + o_succ);
+    rc = batch_decode(g, b, count, d_succ);
+    if (rc == 0 && total) {
+        HIPCHK(hipMemcpyAsync(succ, d_succ, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipStreamSynchronize(g->stream));
+    }
+    for (size_t k = 0; k < deep.size() && rc == 0; k++) {                        // (the range decode reuses the workspace: the batch's results are on the host by now)
+        const DeepRequest& q = deep[k];
+        int32_t d1 = 0; uint64_t got = 0; int64_t dummy = 0;
+        rc = decode_range_impl(g, nodes[q.index], nodes[q.index] + 1, &d1, q.arcs ? succ + q.at : &dummy, q.arcs ? q.arcs : 1, &got, false);
+        if (rc == 0 && got != q.arcs) rc = BVG_E_STATE;
+    }
+    return rc;
+}
+
+}  // namespace bvghost
+
 extern "C" {
 
 int bvg_abi_version(void) { return BVG_ABI_VERSION; }
@@ -208,73 +378,6 @@ int bvg_outdegrees(bvg_graph* g, int64_t from, int64_t to, int32_t* out) {
     return e == hipSuccess ? 0 : BVG_E_HIP;
 }
 
-// Per-handle device workspace for the materialising calls: grown on demand, kept between calls (a NodeIterator asks for batch
-// after batch of the same size; a fresh hipMalloc / hipFree pair per buffer and call cost more than the decode of a small batch).
-static int dr_ensure(bvg_graph* g, size_t bytes) {
-    if (bytes <= g->dr_ws_bytes) return 0;
-    if (g->dr_ws) { (void)hipFree(g->dr_ws); g->dr_ws = nullptr; g->dr_ws_bytes = 0; }
-    const size_t want = bytes + bytes / 4;
-    if (hipMalloc(&g->dr_ws, want) != hipSuccess) {
-        (void)hipGetLastError();
-        if (hipMalloc(&g->dr_ws, bytes) != hipSuccess) { (void)hipGetLastError(); g->dr_ws = nullptr; return BVG_E_NOMEM; }
-        g->dr_ws_bytes = bytes; return 0;
-    }
-    g->dr_ws_bytes = want;
-    return 0;
-}
-
-static int decode_range_impl(bvg_graph* g, int64_t from, int64_t to, int32_t* outdeg, int64_t* succ, uint64_t cap, uint64_t* n_succ, bool dev, bool narrow = false) {
-    if (!g) return BVG_E_ARG;
-    Shared* sh = g->sh;
-    if (narrow && (dev || (uint64_t)sh->p.nodes + g->node_base > 0xFFFFFFFFull)) return BVG_E_UNSUPPORTED;   // 32-bit ids: host path, every id below 2^32 - 1 (0xFFFFFFFF stands for the -1 of a malformed stream, never for a node)
-    if (from < 0 || to > sh->p.nodes || from > to) return BVG_E_ARG;               // BVG:863,1000,1128
-    if (from == to) { if (n_succ) *n_succ = 0; return 0; }
-    HIPCHK(hipSetDevice(sh->device));
-    const int64_t cnt = to - from;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // workspace: [cum | scan tmp | deg (unless the caller's device buffer takes them)] and, for host callers, the successors behind them
-    const size_t o_cum = 0, o_tmp = o_cum + al(((size_t)cnt + 1) * sizeof(uint64_t)), o_deg = o_tmp + al(scan_tmp_elems(cnt) * sizeof(uint64_t));
-    const size_t o_succ = o_deg + al((size_t)cnt * sizeof(int32_t));
-    int rc = dr_ensure(g, o_succ); if (rc) return rc;
-    auto at = [&](size_t off) { return (char*)g->dr_ws + off; };
-    int32_t* d_deg = (dev && outdeg) ? outdeg : (int32_t*)at(o_deg);
-    uint64_t* d_cum = (uint64_t*)at(o_cum);
-    launch_outdegrees(sh->d_graph, sh->nbytes, sh->offs, from, to, sh->p.outdegree_coding, d_deg, nullptr, g->stream);
-    launch_exclusive_scan(d_deg, d_cum, cnt, (uint64_t*)at(o_tmp), g->stream);
-    uint64_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, d_cum + cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
-    if (n_succ) *n_succ = total;
-    if (total > cap || (!succ && total > 0)) {          // query / too small: report the size (and the outdegrees)
-        if (outdeg && !dev) HIPCHK(hipMemcpy(outdeg, d_deg, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
-        return BVG_E_CAPACITY;
-    }
-    int64_t* d_succ = succ;
-    if (!dev) {
-        const size_t per = sizeof(int64_t) + (narrow ? sizeof(uint32_t) : 0);
-        if (o_succ + (size_t)(total ? total : 1) * per + 256 > g->dr_ws_bytes) {
-            // growing moves the workspace: the prefix sums are recomputed rather than copied (two tiny kernels)
-            rc = dr_ensure(g, o_succ + (size_t)(total ? total : 1) * per + 256); if (rc) return rc;
-            d_deg = (int32_t*)at(o_deg); d_cum = (uint64_t*)at(o_cum);
-            launch_outdegrees(sh->d_graph, sh->nbytes, sh->offs, from, to, sh->p.outdegree_coding, d_deg, nullptr, g->stream);
-            launch_exclusive_scan(d_deg, d_cum, cnt, (uint64_t*)at(o_tmp), g->stream);
-        }
-        d_succ = (int64_t*)at(o_succ);
-    }
-    rc = run_decode(g, from, to, true, d_cum, d_succ, d_deg, nullptr);
-    if (rc == 0 && !dev) {
-        // device -> host on the handle's stream: at PCIe rate when the caller's buffers are page-locked (bvg_host_alloc)
-        if (total && narrow) {
-            uint32_t* d32 = (uint32_t*)at(o_succ + al((size_t)total * sizeof(int64_t)));
-            launch_narrow_succ(d_succ, d32, total, g->stream);
-            HIPCHK(hipMemcpyAsync(succ, d32, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, g->stream));
-        } else if (total) HIPCHK(hipMemcpyAsync(succ, d_succ, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-        if (outdeg) HIPCHK(hipMemcpyAsync(outdeg, d_deg, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-        HIPCHK(hipStreamSynchronize(g->stream));
-    }
-    return rc;
-}
-
 int bvg_decode_range(bvg_graph* g, int64_t from, int64_t to, int32_t* outdeg, int64_t* succ, uint64_t succ_cap, uint64_t* n_succ) {
     return guarded([&] { return decode_range_impl(g, from, to, outdeg, succ, succ_cap, n_succ, false); });
 }
@@ -292,75 +395,6 @@ void* bvg_host_alloc(size_t bytes) {
 }
 void bvg_host_free(void* p) { if (p) (void)hipHostFree(p); }
 
-static int bvg_successors_batch_impl(bvg_graph* g, const int64_t* nodes, int64_t count, int32_t* outdeg, int64_t* succ, uint64_t succ_cap, uint64_t* n_succ) {
-    if (!g || (!nodes && count) || count < 0) return BVG_E_ARG;
-    Shared* sh = g->sh;
-    for (int64_t i = 0; i < count; i++) if (nodes[i] < 0 || nodes[i] >= sh->p.nodes) return BVG_E_ARG;      // BVG:863
-    if (n_succ) *n_succ = 0;
-    if (count == 0) return 0;
-    if (count > 0x3FFFFFFF) return BVG_E_ARG;
-    HIPCHK(hipSetDevice(sh->device));
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t c = (size_t)count;
-    const size_t o_nodes = 0, o_deg = o_nodes + al(c * sizeof(int64_t)), o_first = o_deg + al(c * sizeof(int32_t)), o_cum = o_first + al((2 * c + 1) * sizeof(uint64_t));
-    const size_t o_tmp = o_cum + al((c + 1) * sizeof(uint64_t)), o_halo = o_tmp + al(scan_tmp_elems(count) * sizeof(uint64_t)), o_mask = o_halo + al(2 * c * sizeof(uint32_t));
-    const size_t o_succ = o_mask + al(2 * c * sizeof(uint64_t));
-    int rc = dr_ensure(g, o_succ); if (rc) return rc;
-    auto at = [&](size_t off) { return (char*)g->dr_ws + off; };
-    auto prepare = [&]() -> int {
-        HIPCHK(hipMemcpyAsync(at(o_nodes), nodes, c * sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
-        launch_outdegrees_gather(sh->d_graph, sh->nbytes, sh->offs, (const int64_t*)at(o_nodes), count, sh->p.outdegree_coding, (int32_t*)at(o_deg), (uint64_t*)at(o_first), g->stream);
-        launch_exclusive_scan((const int32_t*)at(o_deg), (uint64_t*)at(o_cum), count, (uint64_t*)at(o_tmp), g->stream);
-        launch_plan_halo(sh->d_graph, sh->nbytes, sh->offs, sh->p.nodes, (const uint64_t*)at(o_first), (uint32_t)(2 * count), sh->p.window_size, codings_of(sh->p), (uint32_t*)at(o_halo), (uint64_t*)at(o_mask), g->stream);
-        return 0;
-    };
-    rc = prepare(); if (rc) return rc;
-    uint64_t total = 0;
-    std::vector<uint32_t> halo(2 * c);
-    HIPCHK(hipMemcpyAsync(&total, (uint64_t*)at(o_cum) + count, sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(halo.data(), at(o_halo), halo.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
-    if (n_succ) *n_succ = total;
-    if (outdeg) HIPCHK(hipMemcpy(outdeg, at(o_deg), c * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (total > succ_cap || (!succ && total > 0)) return BVG_E_CAPACITY;
-    // A request whose reference chain reaches more than 64 nodes back (possible with maxrefcount x window > 64) does not fit a
-    // request block's halo: it is taken out of the batch (an empty block) and decoded afterwards through the graph's block plan,
-    // whose blocks are cut so that every chain fits (successors(x) recurses as deep as the chain goes, BVG:1084).
-    std::vector<int64_t> deep;
-    for (int64_t i = 0; i < count; i++) if (halo[2 * (size_t)i] == 0xFFFFFFFFu) deep.push_back(i);
-    std::vector<uint64_t> hcum;
-    if (!deep.empty()) {
-        hcum.resize(c + 1);
-        HIPCHK(hipMemcpy(hcum.data(), at(o_cum), (c + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    auto blank_deep = [&]() -> int {
-        for (int64_t i : deep) {
-            const uint64_t pair[2] = {(uint64_t)nodes[i], (uint64_t)nodes[i]}; const uint32_t hz[2] = {0u, 0u};
-            HIPCHK(hipMemcpy((uint64_t*)at(o_first) + 2 * (size_t)i, pair, sizeof pair, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy((uint32_t*)at(o_halo) + 2 * (size_t)i, hz, sizeof hz, hipMemcpyHostToDevice));
-        }
-        return 0;
-    };
-    rc = blank_deep(); if (rc) return rc;
-    if (o_succ + (size_t)(total ? total : 1) * sizeof(int64_t) > g->dr_ws_bytes) {
-        rc = dr_ensure(g, o_succ + (size_t)(total ? total : 1) * sizeof(int64_t)); if (rc) return rc;
-        rc = prepare(); if (rc) return rc;                                   // the workspace moved: redo the (cheap) preparation in the new one
-        rc = blank_deep(); if (rc) return rc;
-    }
-    BatchPlan bp{(const uint64_t*)at(o_first), (const uint32_t*)at(o_halo), (const uint64_t*)at(o_mask), (uint32_t)count};
-    rc = run_decode(g, 0, sh->p.nodes, true, (const uint64_t*)at(o_cum), (int64_t*)at(o_succ), nullptr, nullptr, &bp);
-    if (rc == 0 && total) {
-        HIPCHK(hipMemcpyAsync(succ, at(o_succ), (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-        HIPCHK(hipStreamSynchronize(g->stream));
-    }
-    for (size_t k = 0; k < deep.size() && rc == 0; k++) {                        // (the range decode reuses the workspace: the batch's results are on the host by now)
-        const int64_t i = deep[k]; const uint64_t want = hcum[(size_t)i + 1] - hcum[(size_t)i];
-        int32_t d1 = 0; uint64_t got = 0; int64_t dummy = 0;
-        rc = decode_range_impl(g, nodes[i], nodes[i] + 1, &d1, want ? succ + hcum[(size_t)i] : &dummy, want ? want : 1, &got, false);
-        if (rc == 0 && got != want) rc = BVG_E_STATE;
-    }
-    return rc;
-}
 
 static int bvg_scan_impl(bvg_graph* g, int64_t from, int64_t to, bvg_scan_result* out) {
     if (!g || !out) return BVG_E_ARG;

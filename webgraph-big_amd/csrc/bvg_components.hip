@@ -163,15 +163,6 @@ __global__ void cc_remap_kernel(int64_t* comp, int64_t n, const uint64_t* newidx
     CC_FOR(x, n) comp[x] = (int64_t)newidx[comp[x]];
 }
 
-// per batch bound j: the prefix sum at the bound and at the node before it (the arcs of a segment without its last list)
-__global__ void cc_gather_bounds_kernel(const uint64_t* cum, const uint64_t* first, uint64_t nb, uint64_t* at, uint64_t* before) {
-    CC_FOR(j, nb + 1) {
-        const uint64_t b = first[j];
-        at[j] = cum[b];
-        before[j] = b ? cum[b - 1] : 0;
-    }
-}
-
 inline unsigned grid(int64_t n, int64_t per) { const int64_t b = (n + per - 1) / per; return (unsigned)(b < 1 ? 1 : (b > (1 << 18) ? (1 << 18) : b)); }   // (the kernels stride)
 
 }  // namespace
@@ -183,62 +174,6 @@ namespace {
 using bvghost::DevBuf;
 
 constexpr uint64_t kMaxBatchArcs = 1ull << 32;     // 32 GiB of successors: the per-batch overhead (a plan lookup, two syncs) is already negligible
-
-constexpr int64_t kMaxBatchNodes = 1ll << 30;      // node ranges of a launch stay well below 2^32 work-items
-
-struct Batch { int64_t lo, hi; uint64_t arcs; };
-
-// outdegrees of [from, to) into out[0, to - from): launch_outdegrees runs one work-item per node, so longer ranges go in pieces
-void outdegrees_of(bvg_graph* g, int64_t from, int64_t to, int32_t* out) {
-    Shared* sh = g->sh;
-    for (int64_t a = from; a < to; a += kMaxBatchNodes)
-        launch_outdegrees(sh->d_graph, sh->nbytes, sh->offs, a, std::min(to, a + kMaxBatchNodes), sh->p.outdegree_coding, out + (a - from), nullptr, g->stream);
-}
-
-// [0, n) cut into node ranges of at most `per` arcs each, except that a list longer than that forms a batch on its own.  The whole
-// graph's outdegrees and their prefix sums are computed on the device; the cut points are the lower bounds of j * per in the prefix
-// sums (launch_plan_boundaries), so a segment holds < per arcs before its last list and is split before that list when the whole
-// exceeds per.
-int plan_batches(bvg_graph* g, uint64_t per, std::vector<Batch>& out, uint64_t* arcs_out, uint64_t* longest_out) {
-    Shared* sh = g->sh; const int64_t n = sh->p.nodes;
-    DevBuf deg, cum, tmp;
-    if (deg.alloc((size_t)n * 4) || cum.alloc(((size_t)n + 1) * 8) || tmp.alloc(scan_tmp_elems(n) * 8)) return BVG_E_NOMEM;
-    outdegrees_of(g, 0, n, (int32_t*)deg.p);
-    launch_exclusive_scan((const int32_t*)deg.p, (uint64_t*)cum.p, n, (uint64_t*)tmp.p, g->stream);
-    uint64_t arcs = 0;
-    HIPCHK(hipMemcpyAsync(&arcs, (uint64_t*)cum.p + n, 8, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
-    *arcs_out = arcs; *longest_out = 0;
-    out.clear();
-    if (arcs == 0) return 0;
-    if (per == 0) per = 1;
-    const uint64_t nb = (arcs + per - 1) / per;
-    DevBuf first, at, before;
-    if (first.alloc((nb + 1) * 8) || at.alloc((nb + 1) * 8) || before.alloc((nb + 1) * 8)) return BVG_E_NOMEM;
-    launch_plan_boundaries(Offsets{nullptr, nullptr, (const uint64_t*)cum.p}, n, per, nb, (uint64_t*)first.p, g->stream);
-    hipLaunchKernelGGL(cc_gather_bounds_kernel, dim3(grid((int64_t)nb + 1, 256)), dim3(256), 0, g->stream, (const uint64_t*)cum.p, (const uint64_t*)first.p, nb,
-                       (uint64_t*)at.p, (uint64_t*)before.p);
-    std::vector<uint64_t> hf(nb + 1), ha(nb + 1), hb(nb + 1);
-    HIPCHK(hipMemcpyAsync(hf.data(), first.p, (nb + 1) * 8, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(ha.data(), at.p, (nb + 1) * 8, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(hb.data(), before.p, (nb + 1) * 8, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
-    for (uint64_t j = 0; j < nb; j++) {
-        const uint64_t b0 = hf[j], b1 = hf[j + 1];
-        if (b1 <= b0) continue;
-        const uint64_t all = ha[j + 1] - ha[j], last = ha[j + 1] - hb[j + 1];     // arcs of the segment, of its last list
-        if (all <= per || b1 - b0 == 1) out.push_back(Batch{(int64_t)b0, (int64_t)b1, all});
-        else { out.push_back(Batch{(int64_t)b0, (int64_t)b1 - 1, all - last}); out.push_back(Batch{(int64_t)b1 - 1, (int64_t)b1, last}); }
-    }
-    std::vector<Batch> cut;                                                  // (and at most kMaxBatchNodes nodes each: runs of empty lists)
-    for (const Batch& b : out) {
-        if (b.hi - b.lo <= kMaxBatchNodes) { cut.push_back(b); continue; }
-        for (int64_t a = b.lo; a < b.hi; a += kMaxBatchNodes) cut.push_back(Batch{a, std::min(b.hi, a + kMaxBatchNodes), b.arcs});   // (arcs: a bound)
-    }
-    out.swap(cut);
-    for (const Batch& b : out) if (b.arcs > *longest_out) *longest_out = b.arcs;
-    return 0;
-}
 
 template <typename T> int components_t(bvg_graph* g, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components, bool dev) {
     Shared* sh = g->sh; const int64_t n = sh->p.nodes;

@@ -232,6 +232,24 @@ struct BatchPlan { const uint64_t* d_first; const uint32_t* d_halo; const uint64
 int run_decode(bvg_graph* g, int64_t from, int64_t to, bool materialise, const uint64_t* d_cum, int64_t* d_succ, int32_t* d_outdeg,
                bvg_scan_result* res, const BatchPlan* batch = nullptr, const std::shared_ptr<Plan>* use_plan = nullptr);
 
+// ---- bvg_plan.hip: the graph (or any list of lists with prefix sums on the device) cut into arc-bounded ranges (bvg_components, bvg_bfs_visit)
+constexpr int64_t kMaxBatchNodes = 1ll << 30;      // node ranges of a launch stay well below 2^32 work-items
+struct Batch { int64_t lo, hi; uint64_t arcs; };
+void outdegrees_of(bvg_graph* g, int64_t from, int64_t to, int32_t* out);
+int cut_batches(bvg_graph* g, const uint64_t* d_cum, int64_t n, uint64_t arcs, uint64_t per, std::vector<Batch>& out, uint64_t* longest_out);
+int plan_batches(bvg_graph* g, uint64_t per, std::vector<Batch>& out, uint64_t* arcs_out, uint64_t* longest_out);
+
+// ---- bvg_api.hip: what bvg_successors_batch and the frontier route of bvg_bfs_visit share (described there)
+int decode_range_impl(bvg_graph* g, int64_t from, int64_t to, int32_t* outdeg, int64_t* succ, uint64_t cap, uint64_t* n_succ, bool dev, bool narrow = false);
+constexpr int64_t kMaxBatchRequests = 0x3FFFFFFF;
+struct BatchBufs { int32_t* deg; uint64_t* first; uint64_t* cum; uint64_t* tmp; uint32_t* halo; uint64_t* mask; uint64_t* deep; size_t end; };   // device arrays of one batch; end: their bytes
+struct DeepRequest { int64_t index; uint64_t at, arcs; };                  // request `index`: its list belongs at d_succ + at and holds `arcs` successors
+size_t batch_bufs_bytes(int64_t count);
+BatchBufs batch_bufs_at(char* base, int64_t count);
+int batch_degrees(bvg_graph* g, const BatchBufs& b, const int64_t* d_nodes, int64_t count, uint64_t* total);
+int batch_halos(bvg_graph* g, const BatchBufs& b, const int64_t* d_nodes, int64_t count, std::vector<DeepRequest>& deep);
+int batch_decode(bvg_graph* g, const BatchBufs& b, int64_t count, int64_t* d_succ);
+
 // The granularity of a graph's skip index: lists of >= `smin` residuals hold one entry per 2^shift residuals.  A residual pass lasts as long as its longest task, so the
 // threshold matters as much as the spacing: 16 / 16 (a list of 16-23 residuals is two tasks instead of one of up to 23 steps) gains on every shape over rounds 1-3's 24 / 16
 // -- w0 +7.2 %, uk +3.8 %, web +2.6 %, eu +1.5 %, eu15 +1.0 % -- for 0.1-8 % more entries.  A sparse graph's pass holds few tasks, and one entry per 8 residuals from

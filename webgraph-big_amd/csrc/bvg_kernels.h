@@ -184,6 +184,9 @@ void launch_plan_boundaries(Offsets offsets, int64_t n, uint64_t block_bits, uin
 void launch_plan_halo(const uint8_t* graph, uint64_t limit_byte, Offsets offsets, int64_t n, const uint64_t* first, uint32_t nblk,
                       int window, Codings cod, uint32_t* halo, uint64_t* mask, hipStream_t s);
 
+// batch requests whose chain does not fit a request block: blanked ({x, x}, no halo) and listed in deep[] = {count, then {index, cum[index], outdegree} each}
+void launch_batch_deep(const int64_t* nodes, int64_t count, const uint64_t* cum, uint64_t* first, uint32_t* halo, uint64_t* deep, hipStream_t s);
+
 // plan: largest outdegree among the nodes a block decodes (its own + its halo): predicts the LDS tier it needs
 void launch_plan_longest(Offsets offsets, const uint64_t* first, uint32_t nblk, uint64_t* node, uint64_t* bits, hipStream_t s);
 void launch_plan_maxd(const uint8_t* graph, uint64_t limit_byte, Offsets offsets, const uint64_t* first, const uint32_t* halo, uint32_t nblk,

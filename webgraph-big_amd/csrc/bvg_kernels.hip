@@ -680,6 +680,21 @@ void launch_plan_halo(const uint8_t* graph, uint64_t limit_byte, Offsets offsets
     hipLaunchKernelGGL(plan_halo_kernel, dim3((nblk + 127) / 128), dim3(128), 0, s, graph, limit_byte, offsets, n, first, nblk, window, cod, halo, mask);
 }
 
+// The requests of a batch whose reference chain does not fit a request block (plan_halo_kernel reports halo 0xFFFFFFFF): each becomes an empty block
+// ({x, x} with no halo) and is listed for the caller -- deep[0] = their number, then {request index, cum[index], outdegree} each, in any order.
+__global__ void batch_deep_kernel(const int64_t* nodes, int64_t count, const uint64_t* cum, uint64_t* first, uint32_t* halo, uint64_t* deep) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count || halo[2 * i] != 0xFFFFFFFFu) return;
+    const uint64_t k = (uint64_t)atomicAdd((unsigned long long*)deep, 1ull);
+    deep[1 + 3 * k] = (uint64_t)i; deep[2 + 3 * k] = cum[i]; deep[3 + 3 * k] = cum[i + 1] - cum[i];
+    first[2 * i] = first[2 * i + 1] = (uint64_t)nodes[i];
+    halo[2 * i] = halo[2 * i + 1] = 0u;
+}
+void launch_batch_deep(const int64_t* nodes, int64_t count, const uint64_t* cum, uint64_t* first, uint32_t* halo, uint64_t* deep, hipStream_t s) {
+    if (count <= 0) return;
+    hipLaunchKernelGGL(batch_deep_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, nodes, count, cum, first, halo, deep);
+}
+
 // the longest record of every block: its node and its length in bits (one wavefront per block)
 __global__ void plan_longest_kernel(Offsets offsets, const uint64_t* first, uint32_t nblk, uint64_t* node, uint64_t* bits) {
     const uint32_t k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);

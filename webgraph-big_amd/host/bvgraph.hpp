@@ -178,6 +178,8 @@ public:
         if (sizes) sizes->resize((size_t)count);
         return (int64_t)count;
     }
+    // breadth-first visits on the device (algo/ParallelBreadthFirstVisit.java): the class is below
+    inline class ParallelBreadthFirstVisit breadthFirstVisit(bool parent = false);
     NodeIterator nodeIterator(int64_t from = 0) { return NodeIterator(shared_from_this(), from, INT64_MAX); }   // BVGraph.java:1257
     std::vector<NodeIterator> splitNodeIterators(int howMany) {                            // ImmutableGraph.java:405-436
         std::vector<NodeIterator> v; const int64_t n = p_.nodes, m = (n + howMany - 1) / howMany;
@@ -191,6 +193,40 @@ public:
         bvg_scan_result r; check(bvg_scan(h_, from, to < 0 ? p_.nodes : to, &r), "scan"); return r;
     }
 };
+
+// ParallelBreadthFirstVisit (algo/ParallelBreadthFirstVisit.java) over bvg_bfs_*: marker / round / queue / cutPoints live on the device
+// between visits; inside a level the queue is in increasing id, and with parent = true a node's parent is the smallest node of the
+// previous level that has it as a successor.  dist() is the level of every node of the last visit (-1: not reached).
+class ParallelBreadthFirstVisit {
+    bvg_bfs* v_ = nullptr; int64_t n_ = 0;
+public:
+    ParallelBreadthFirstVisit(BVGraph& g, bool parent) : n_(g.numNodes()) { check(bvg_bfs_create(g.handle(), parent ? BVG_BFS_PARENT : 0u, &v_), "bfs_create"); }
+    ParallelBreadthFirstVisit(ParallelBreadthFirstVisit&& o) noexcept : v_(o.v_), n_(o.n_) { o.v_ = nullptr; }
+    ParallelBreadthFirstVisit(const ParallelBreadthFirstVisit&) = delete;
+    ParallelBreadthFirstVisit& operator=(const ParallelBreadthFirstVisit&) = delete;
+    ~ParallelBreadthFirstVisit() { bvg_bfs_close(v_); }
+    void clear() { check(bvg_bfs_clear(v_), "bfs_clear"); }
+    int64_t visit(int64_t start) { uint64_t k = 0; check(bvg_bfs_visit(v_, start, &k), "bfs_visit"); return (int64_t)k; }
+    void visitAll() { check(bvg_bfs_visit_all(v_), "bfs_visit_all"); }
+    int64_t round() const { int64_t r = 0; check(bvg_bfs_info(v_, &r, nullptr, nullptr), "bfs_info"); return r; }
+    int64_t maxDistance() const { uint64_t c = 0; check(bvg_bfs_info(v_, nullptr, nullptr, &c), "bfs_info"); return (int64_t)c - 2; }
+    std::vector<int64_t> queue() const {
+        uint64_t q = 0; check(bvg_bfs_info(v_, nullptr, &q, nullptr), "bfs_info");
+        std::vector<int64_t> out((size_t)q);
+        if (q) check(bvg_bfs_get(v_, nullptr, out.data(), q, nullptr, 0, nullptr), "bfs_get");
+        return out;
+    }
+    std::vector<uint64_t> cutPoints() const {
+        uint64_t c = 0; check(bvg_bfs_info(v_, nullptr, nullptr, &c), "bfs_info");
+        std::vector<uint64_t> out((size_t)c);
+        if (c) check(bvg_bfs_get(v_, nullptr, nullptr, 0, out.data(), c, nullptr), "bfs_get");
+        return out;
+    }
+    std::vector<int64_t> marker() const { std::vector<int64_t> out((size_t)n_); if (n_) check(bvg_bfs_get(v_, out.data(), nullptr, 0, nullptr, 0, nullptr), "bfs_get"); return out; }
+    std::vector<int32_t> dist() const { std::vector<int32_t> out((size_t)n_); if (n_) check(bvg_bfs_get(v_, nullptr, nullptr, 0, nullptr, 0, out.data()), "bfs_get"); return out; }
+    int64_t nodeAtMaxDistance() const { const std::vector<int64_t> q = queue(); if (q.empty()) throw std::out_of_range("nodeAtMaxDistance: empty queue"); return q.back(); }
+};
+inline ParallelBreadthFirstVisit BVGraph::breadthFirstVisit(bool parent) { return ParallelBreadthFirstVisit(*this, parent); }
 
 inline NodeIterator::NodeIterator(std::shared_ptr<BVGraph> g, int64_t from, int64_t upperBound, int64_t batchNodes)
     : g_(std::move(g)), from_(from), curr_(from - 1), batch_(batchNodes) {
