@@ -297,7 +297,12 @@ int bvg_labels_decode_range_dev(bvg_labels* l, int64_t from, int64_t to, const v
  * with the gamma / delta coded gaps of BVG:2228,2311).  p gives windowsize, maxrefcount (-1 = unbounded), minintervallength, zetak and
  * the codings (nodes / arcs are ignored).  chunk_nodes > 0 compresses ranges of that many nodes with a fresh window each, as the
  * reference's multi-threaded store does (BVG:2404-2457); 0 = one range = the single-threaded store, byte for byte.
- * *graph / *offsets are malloc'ed (bvg_free).  BVG_E_ARG for lists that are not strictly increasing or leave [0, nodes). */
+ * minintervallength = 1 means runs of two or more consecutive extras, as in the reference (only v[i] + 1 == v[i + 1] opens an interval,
+ * BVG:1604): a lone extra is a residual whatever the minimum; 0 disables intervals.  windowsize above 127 is BVG_E_UNSUPPORTED.
+ * *graph / *offsets are malloc'ed (bvg_free).  The input is checked on the device before any list is read; BVG_E_ARG, and nothing
+ * written, for offsets that do not start at 0 (adj_off[0] != 0: adj_off indexes adj itself, not a slice of a larger array), decrease,
+ * pass adj_off[nodes] or span more than 2^31 - 1 successors, and for lists that are not strictly increasing or leave [0, nodes).
+ * adj must hold adj_off[nodes] elements (it may be NULL only if that is 0). */
 int bvg_store(const bvg_params* p, int64_t nodes, const uint64_t* adj_off, const int64_t* adj, int64_t chunk_nodes, int device,
               uint8_t** graph, uint64_t* graph_bytes, uint64_t** offsets);
 void bvg_free(void* p);

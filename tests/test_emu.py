@@ -71,6 +71,48 @@ def test_malformed_stream_suite_on_the_emulator(emu_lib):
     assert out.returncode == 0 and " passed" in out.stdout, out.stdout[-3000:] + out.stderr[-2000:]
 
 
+def _gpu_file_on_the_emulator(emu_lib, order, args, **env):
+    e = dict(os.environ, BVG_HIP_LIB=emu_lib, BVG_TEST_KNOBS="1", BVG_EMU_ORDER=order, **env)
+    out = subprocess.run([sys.executable, "-m", "pytest", "-m", "gpu", "-x", "-q", "-s", "-p", "no:cacheprovider"] + args, env=e, capture_output=True, text=True, timeout=1500, cwd=ROOT)
+    assert out.returncode == 0 and " passed" in out.stdout and "skipped" not in out.stdout, out.stdout[-4000:] + out.stderr[-2000:]
+
+
+# what of tests/test_gpu_store.py each lane order runs here (the GPU run has all of it)
+STORE_ON_THE_EMULATOR = {
+    "fwd": "not 100000 and not cnr2000 and not round_trip and not fuzz_6000 and not test_device_store_equals_cpu_tooling",
+    "rev": "windows_around or chunks_that or equally_cheap or one_tile or min_interval",
+}
+
+
+@pytest.mark.parametrize("order", ["fwd", "rev"])
+def test_device_compressor_suite_on_the_emulator(emu_lib, order):
+    """tests/test_gpu_store.py -- the device compressor against the CPU tooling, byte for byte, and its bytes through the oracle -- on the CPU.
+    Cut from the emulated selection, for time only (all of them run on the GPU): the list of over 100 000 successors (its three cases take
+    longer here than the rest together), the cnr-2000 fixture (39 s here), the 20 000-node round trip through the decoder (7 s), the
+    6 000-node shapes (20 s) and the original 7 000-node parameter sets (18 x 1.1 s; the same parameters run here on 1 500 nodes).  The
+    reversed lane order is for enc_choose_kernel, which orders its LDS traffic with enc_wave_sync() alone (the other three kernels have no
+    cross-lane traffic at all): it runs the tests that vary the window, the chunk and the chains, the forward order everything kept.
+    Measured on one machine: test_malformed_stream_suite_on_the_emulator 93 s (at the commit before this test); this test 42 s (fwd) +
+    23 s (rev), the randomised test below 3 s + 5 s: 73 s together."""
+    _gpu_file_on_the_emulator(emu_lib, order, [os.path.join(ROOT, "tests", "test_gpu_store.py"), "-k", STORE_ON_THE_EMULATOR[order]])
+
+
+@pytest.mark.parametrize("order,first", [("fwd", 0), ("rev", 10)])
+def test_randomised_device_compressor_on_the_emulator(emu_lib, order, first):
+    """tests/test_gpu_store_fuzz.py, ten cases per lane order (0.33 s a case here); the two orders run different cases."""
+    _gpu_file_on_the_emulator(emu_lib, order, [os.path.join(ROOT, "tests", "test_gpu_store_fuzz.py")], BVG_STORE_FUZZ=str(first + 10), BVG_STORE_FUZZ_FROM=str(first))
+
+
+@pytest.mark.skipif(not os.environ.get("BVG_EMU_ASAN"), reason="opt-in (BVG_EMU_ASAN=1): the AddressSanitizer build of the emulated library takes ~4 minutes to compile")
+def test_compressor_input_check_under_address_sanitizer():
+    """test_degenerate_adjacencies sends offsets that point a million elements past a three-element adjacency: enc_check_kernel must refuse
+    them without reading adj (before the check compared with adj_off[nodes], this run ended in an ASan report)."""
+    subprocess.check_call(["make", "-s", "-j4", "-C", EMU, "asan"])
+    asan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"], text=True).strip()
+    _gpu_file_on_the_emulator(os.path.join(EMU, "libbvgraph_emu_asan.so"), "fwd", [os.path.join(ROOT, "tests", "test_gpu_store.py"), "-k", "degenerate or min_interval or one_tile"],
+                              LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1")
+
+
 def test_randomised_parity_of_the_lean_kernels_on_the_emulator(emu_lib):
     """tests/emu/fuzz_flat.py: random shapes, windows, reference-chain depths, interval lengths, zeta k, LDS geometries (small pools: sub-rows and compaction), records per
     super-row and lane orders; scan_kernel and the experimental flat kernel against the oracle (8 cases here; 90 ran on the final round-5 tree: BVG_EMU_FUZZ=<n> for more)."""

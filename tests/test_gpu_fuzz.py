@@ -93,7 +93,7 @@ def test_random_graphs_parameters_and_tiers(W, tools, oracle, monkeypatch):
         g.close()
         # the device compressor writes the very bytes the CPU tooling wrote
         chunk = int(rng.choice([0, 64, 1000]))
-        if kw["window_size"] <= 64:                                            # (the device compressor's window limit is 127; the tooling's chunked form matches BVG:2404-2457)
+        if kw["window_size"] <= 127:                                           # (the device compressor's window limit is 127; the tooling's chunked form matches BVG:2404-2457)
             ref = st if chunk == 0 else tools.store((off, adj), p, chunk_nodes=chunk, threads=2)
             gb, go = W.store((off, adj), p, chunk_nodes=chunk)
             assert np.array_equal(gb, ref.graph) and np.array_equal(go, ref.offsets), what + (chunk,)

@@ -96,3 +96,47 @@ def test_hand_built_branch_graphs(W, tools, oracle):
             assert og.successors(x).tolist() == l
         deg, succ = og.decode_range(0, len(lists))
         assert succ.tolist() == [v for l in lists for v in l]
+
+
+# intervalize (BVGraph.java:1595-1618) by hand.  It walks the extras v[0..vl); at i it opens an interval only if v[i] + 1 == v[i + 1], counts
+# the run's length j (so j >= 2 whenever j != 0), keeps it if j >= min and otherwise leaves j = that short length; `if (j < min)` then
+# makes v[i] -- alone -- a residual and the walk goes on at i + 1.  Hence, for every minimum:
+#   [5]           no neighbour: j = 0 < min, residual 5.  Also for min = 1: an interval of one element does not exist.
+#   [5, 6]        j = 2: one interval (5, 2) for min 1 and 2; for min 3, 2 < 3 makes 5 a residual, then i = 1 is the last element: 6 too.
+#   [5, 7]        5 + 1 != 7: two residuals.
+#   [5, 6, 7, 9]  j = 3 at i = 0: interval (5, 3) for min 1, 2, 3 (i jumps to 3); 9 is last: residual.
+#   [0, 1, 2, 3]  j = 4: interval (0, 4), no residual; written at node 3 the left extreme is coded as int2nat(0 - 3) = 5.
+_INTERVALIZE_BY_HAND = [    # (node, list, min_interval_length, intervals (left, len), residuals)
+    (0, [5], 1, [], [5]), (0, [5], 2, [], [5]), (0, [5], 3, [], [5]),
+    (0, [5, 6], 1, [(5, 2)], []), (0, [5, 6], 2, [(5, 2)], []), (0, [5, 6], 3, [], [5, 6]),
+    (0, [5, 7], 1, [], [5, 7]), (0, [5, 7], 2, [], [5, 7]), (0, [5, 7], 3, [], [5, 7]),
+    (0, [5, 6, 7, 9], 1, [(5, 3)], [9]), (0, [5, 6, 7, 9], 2, [(5, 3)], [9]), (0, [5, 6, 7, 9], 3, [(5, 3)], [9]),
+    (3, [0, 1, 2, 3], 1, [(0, 4)], []), (3, [0, 1, 2, 3], 2, [(0, 4)], []), (3, [0, 1, 2, 3], 3, [(0, 4)], []),
+]
+
+# The records themselves for min_interval_length = 1, window_size = 0 (BVG:2092-2125: gamma outdegree; no reference field without a window;
+# gamma interval count; per interval gamma(int2nat(left - node)) then gamma(len - min); residuals zeta_3, the first as int2nat(r - node)).
+# gamma(x): with v = x + 1 and b = msb(v), b zeros, a one, the b low bits of v.  zeta_3(x): v = x + 1, h = msb(v) / 3, h zeros, a one, then
+# v - 8^h in 3h + 2 bits if v < 2 * 8^h.
+#   [5] at node 0:     outdegree gamma(1) = 010 | count gamma(0) = 1 | residual zeta_3(int2nat(5) = 10): v = 11, h = 1: 01, 11 - 8 = 3 in 5 bits 00011
+#   [5, 6] at node 0:  outdegree gamma(2) = 011 | count gamma(1) = 010 | left gamma(10): v = 11 = 1011b: 000 1 011 | length gamma(2 - 1) = 010
+_RECORD_BITS_BY_HAND = {(5,): "010" "1" "0100011", (5, 6): "011" "010" "0001011" "010"}
+
+
+@pytest.mark.parametrize("x,l,m,intervals,residuals", _INTERVALIZE_BY_HAND)
+def test_intervalize_against_expectations_computed_by_hand(W, tools, x, l, m, intervals, residuals):
+    """The device compressor is held to this encoder (tests/test_gpu_store.py), this encoder to the reference's fixture at
+    min_interval_length = 3 only: here its intervals are pinned for 1, 2 and 3 to what BVGraph.intervalize does on paper."""
+    from bvrecords import PyBits, Record
+    n = 10
+    lists = [l if y == x else [] for y in range(n)]
+    st = tools.store(lists, W.default_params(min_interval_length=m, window_size=0))
+    assert (st.stats["intervalised"], st.stats["residual"], st.stats["copied"]) == (sum(ln for _, ln in intervals), len(residuals), 0)
+    w = PyBits()
+    Record(len(l), intervals=intervals, residuals=residuals).write(w, x, 0, m, 3, len(l))
+    want = "1" * x + "".join(map(str, w.bits)) + "1" * (n - 1 - x)                    # (an empty list is gamma(0) = 1)
+    assert st.offsets.tolist() == list(range(x + 1)) + [x + len(w) + i for i in range(n - x)]
+    got = "".join(map(str, np.unpackbits(st.graph)[:len(want)]))
+    assert got == want and len(st.graph) == (len(want) + 7) // 8
+    if m == 1 and tuple(l) in _RECORD_BITS_BY_HAND:
+        assert got[x:x + len(w)] == _RECORD_BITS_BY_HAND[tuple(l)]

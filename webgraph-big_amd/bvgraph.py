@@ -184,7 +184,9 @@ def _bfs_fns():
 
 def store(adj, params=None, chunk_nodes=0, device=0):
     """BVGraph.store on the device (bvg_store): adj = (adj_off uint64[n+1], succ int64[m]) or a list of sorted lists.
-    Returns (graph uint8[], offsets uint64[n+1]); byte for byte what the reference's compressor writes."""
+    Returns (graph uint8[], offsets uint64[n+1]); byte for byte what the reference's compressor writes.
+    UnsupportedOperationException for a window above 127; IllegalArgumentException for offsets that do not start at 0, decrease or pass
+    adj_off[n], and for lists that are not strictly increasing or leave [0, n) (include/bvgraph_hip.h: bvg_store)."""
     if isinstance(adj, tuple):
         off = np.ascontiguousarray(adj[0], dtype=np.uint64); succ = np.ascontiguousarray(adj[1], dtype=np.int64)
     else:

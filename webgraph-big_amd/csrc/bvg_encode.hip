@@ -85,7 +85,9 @@ __device__ __forceinline__ void diff_walk(const EncParams& p, int ref, const int
     int64_t run_s = 0, run_l = 0;                                          // the current run of consecutive extras
     auto flush = [&]() {
         if (run_l == 0) return;
-        if (p.min_interval != 0 && run_l >= p.min_interval) c.interval(run_s, run_l);
+        // BVG:1599-1604: only v[i] + 1 == v[i + 1] opens an interval, so a run has two elements or more; a lone extra is a residual
+        // whatever the minimum (min_interval = 1 included)
+        if (p.min_interval != 0 && run_l >= 2 && run_l >= p.min_interval) c.interval(run_s, run_l);
         else for (int64_t t = 0; t < run_l; t++) c.residual(run_s + t);
         run_l = 0;
     };
@@ -260,11 +262,13 @@ __global__ void enc_write_kernel(EncParams p, const uint64_t* adj_off, const int
 }
 
 __global__ void enc_check_kernel(const uint64_t* adj_off, const int64_t* adj, int64_t n, unsigned* bad) {
-    // successor lists must be strictly increasing and inside [0, n) (the reference throws on a duplicate, BVG:2141)
+    // the offsets must describe adj[0 .. adj_off[n]) -- start at 0, never decrease, never pass adj_off[n], which is all the caller
+    // allocated -- and successor lists must be strictly increasing and inside [0, n) (the reference throws on a duplicate, BVG:2141);
+    // nothing of adj is read for a list whose offsets are refused
     const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= n) return;
-    const uint64_t a = adj_off[x], b = adj_off[x + 1];
-    if (b < a || b - a > 0x7FFFFFFFull) { atomicOr(bad, 1u); return; }
+    const uint64_t a = adj_off[x], b = adj_off[x + 1], m = adj_off[n];
+    if (adj_off[0] != 0 || b < a || b > m || b - a > 0x7FFFFFFFull) { atomicOr(bad, 1u); return; }
     for (uint64_t i = a; i < b; i++) { const int64_t v = adj[i]; if (v < 0 || v >= n || (i > a && adj[i - 1] >= v)) { atomicOr(bad, 2u); return; } }
 }
 
