@@ -92,7 +92,10 @@ int bvg_decode_offsets(const uint8_t* obytes, size_t nbytes, int64_t nodes, int 
  * no .offsets file: the index is then derived on the device (BVGraph -O / writeOffsets, BVG:2595-2609) by chunk-parallel speculative
  * walks iterated to the one consistent walk -- measured 0.4-10 s per GiB of stream on 0.25 GiB inputs, the fixed part being the
  * regions that settle one 4 KiB chunk per round (profiles/r03_derive_bench.txt); windows > 127 and streams the parallel walk finds
- * odd take one sequential pass of a single wavefront (~360 s per GiB). */
+ * odd take one sequential pass of a single wavefront (~360 s per GiB).  A stream that cannot be derived is refused with the status the
+ * reference's sequential iterator would end with: BVG_E_STATE for a reference above the window (BVG:701), BVG_E_EOF for a stream that
+ * runs out or whose counts contradict each other.  A reference before node 0 is derived as the reference does it (an empty list there:
+ * BVG:1018, 1030). */
 int bvg_open(const char* basename, int load_mode, int device, bvg_graph** out);
 /* Same from host memory.  offsets: nodes+1 bit positions or NULL (derive on device). */
 int bvg_open_mem(const bvg_params* p, const uint8_t* graph, uint64_t nbytes, const uint64_t* offsets, int device, bvg_graph** out);

@@ -324,6 +324,7 @@ static inline uint64_t read_coded(bvgo_bits* b, int coding, int k) {
 static inline int32_t read_outdegree(const bvgo_graph* g, bvgo_bits* b) { return (int32_t)read_coded(b, g->p.outdegree_coding, 0); }
 static inline int64_t read_reference(const bvgo_graph* g, bvgo_bits* b) {
     uint64_t r = read_coded(b, g->p.reference_coding, 0);
+    if (b->err) return 0;                                                         /* (the read itself threw: EOFException comes first) */
     if (r > (uint64_t)g->p.window_size) { b->err = BVGO_E_STATE; return 0; }      /* BVGraph.java:701 */
     return (int64_t)r;
 }
@@ -706,6 +707,21 @@ int bvgo_decode_range(bvgo_graph* g, int64_t from, int64_t to, int32_t* outdeg, 
     bvgo_iter_free(it);
     if (n_succ) *n_succ = k;
     return (succ && k > cap) ? BVGO_E_ARG : 0;
+}
+
+/* BVGraph.writeOffsets (BVGraph.java:2595-2609): the sequential node iterator from node 0, the bit position of the stream taken
+ * before every nextLong() and once more behind the last record; out has nodes + 1 slots.  A bad stream ends with the status the
+ * iterator itself returns there (out[0 .. the failing node] is then what had been written). */
+int bvgo_write_offsets(bvgo_graph* g, uint64_t* out) {
+    bvgo_iter* it; int r = bvgo_node_iterator(g, 0, &it); if (r) return r;
+    for (int64_t i = g->p.nodes; i-- != 0;) {                                     /* :2602 */
+        *out++ = bvgo_iter_bit_position(it);                                      /* :2603-2604: the gap to the last position */
+        int64_t x = bvgo_iter_next(it);                                           /* :2605 */
+        if (x < 0) { bvgo_iter_free(it); return x < -1 ? (int)x : BVGO_E_EOF; }
+    }
+    *out = bvgo_iter_bit_position(it);                                            /* :2607 */
+    bvgo_iter_free(it);
+    return 0;
 }
 
 /* ------------------------------------------------------------------------------------------ */

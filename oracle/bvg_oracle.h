@@ -115,6 +115,11 @@ void bvgo_iter_free(bvgo_iter* it);
 /* Full drain of [from,to) into caller arrays: outdeg[to-from], succ (cap elements).  Sequential path. */
 int bvgo_decode_range(bvgo_graph* g, int64_t from, int64_t to, int32_t* outdeg, int64_t* succ, uint64_t cap, uint64_t* n_succ);
 
+/* BVGraph.writeOffsets (BVGraph.java:2595-2609; BVGraph -O): the offsets of a graph opened without them, by the sequential node
+ * iterator from node 0 -- the bit position before every record and behind the last.  out: nodes + 1 slots.  Returns the iterator's
+ * own status on a bad stream. */
+int bvgo_write_offsets(bvgo_graph* g, uint64_t* out);
+
 /* Scan checksum: the arc mix function shared (by definition, include/bvgraph_hip.h) with the HIP path. */
 uint64_t bvgo_mix(uint64_t x, uint64_t y);
 /* Sequential scan of [from,to): the SpeedTest loop (test/SpeedTest.java:127-135) plus checksum.

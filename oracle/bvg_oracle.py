@@ -66,6 +66,7 @@ def lib():
         L.bvgo_iter_bit_position.argtypes = [vp]; L.bvgo_iter_bit_position.restype = u64
         L.bvgo_iter_free.argtypes = [vp]
         L.bvgo_decode_range.argtypes = [vp, i64, i64, vp, vp, u64, C.POINTER(u64)]
+        L.bvgo_write_offsets.argtypes = [vp, vp]
         L.bvgo_mix.argtypes = [u64, u64]; L.bvgo_mix.restype = u64
         L.bvgo_scan.argtypes = [vp, i64, i64, u64, C.POINTER(ScanResult)]
         L.bvgo_scan_mt.argtypes = [vp, i64, i64, u64, C.c_int, C.POINTER(ScanResult)]
@@ -166,6 +167,13 @@ class Graph:
         if not p:
             return None
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+
+    def derive_offsets(self):
+        """BVGraph.writeOffsets (BVGraph.java:2595-2609): nodes + 1 bit positions from the sequential iterator alone (the graph may have
+        been opened without offsets); OracleError with the iterator's status on a bad stream."""
+        out = np.zeros(self.params.nodes + 1, dtype=np.uint64)
+        _chk(lib().bvgo_write_offsets(self._h, out.ctypes.data))
+        return out
 
     def graph_bytes(self):
         n = C.c_uint64()

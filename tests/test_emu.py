@@ -103,6 +103,52 @@ def test_randomised_device_compressor_on_the_emulator(emu_lib, order, first):
     _gpu_file_on_the_emulator(emu_lib, order, [os.path.join(ROOT, "tests", "test_gpu_store_fuzz.py")], BVG_STORE_FUZZ=str(first + 10), BVG_STORE_FUZZ_FROM=str(first))
 
 
+# what of tests/test_gpu_derive.py each lane order runs here (the GPU run has all of it)
+DERIVE_ON_THE_EMULATOR = {
+    "fwd": "truncated or more_nodes or fewer_nodes or reference_ or contradict or unary or codes_of or legal_but or degenerate or (streams_that and default) "
+           "or (parameter_space and (zeta-warm0_list or golomb-warm0_crawl)) or (blind and intervals-as_is-warm0_crawl)",
+    "rev": "truncated or reference_ or contradict or (parameter_space and (codings-warm0_list or intervals-default)) or (streams_that and warm0_crawl) "
+           "or (chunks_that and warm0_list) or (blind and residuals-as_is-warm0_list)",
+}
+
+
+@pytest.mark.parametrize("order", ["fwd", "rev"])
+def test_offsets_derivation_suite_on_the_emulator(emu_lib, order):
+    """tests/test_gpu_derive.py -- both walks of the offsets derivation against the encoder's offsets and the oracle's derivation -- on the CPU.
+    The parallel walk keeps per-lane outdegree rings in LDS at a stride of 64 dwords and derive_crawl_kernel shares its table of code lengths
+    behind a __syncthreads(); the sequential walk shares two LDS rings between all lanes: the reversed lane order and the exact-size LDS block
+    are for these.  Cut from the emulated selection, for time only (all of it runs on the GPU): the sweep of 72 alignments (36 s per group of
+    eight here), the blind states but one case per order (20 - 28 s each), most groups of the parameter space.  The status-parity cases
+    (streams that are wrong) run here in full, in both orders, before any GPU sees them.
+    Found here, not on the GPU: through thousands of empty records the emulator's lanes drifted more than a ring of outdegrees apart in
+    derive_offsets_kernel (bvg_derive_seq.hip now keeps them within 64 nodes with a barrier).
+    Measured on one machine, next to the figures of test_device_compressor_suite_on_the_emulator: 70 s (fwd) + 75 s (rev),
+    the randomised test below 5 s + 11 s: 161 s together, against the compressor selection's 73 s."""
+    _gpu_file_on_the_emulator(emu_lib, order, [os.path.join(ROOT, "tests", "test_gpu_derive.py"), "-k", DERIVE_ON_THE_EMULATOR[order]])
+
+
+# the streams that are wrong or odd: what the walks read at and behind the end of a stream
+DERIVE_UNDER_ASAN = "truncated or more_nodes or fewer_nodes or run_of_zeros or reference_ or contradict or unary or legal_but"
+
+
+@pytest.mark.skipif(not os.environ.get("BVG_EMU_ASAN"), reason="opt-in (BVG_EMU_ASAN=1): the AddressSanitizer build of the emulated library takes ~4 minutes to compile")
+def test_offsets_derivation_of_wrong_streams_under_address_sanitizer():
+    """The status-parity cases of tests/test_gpu_derive.py -- truncated streams, a run of zeros to the end, more nodes than records, contradicting
+    counts, references out of range -- and the unary codes beyond 64 bits under ASan + UBSan, before they go to a GPU: the walks read ahead of
+    the position (BitBuf: the two words behind the current one; derive_crawl_kernel: nine bytes from every bit of the chunk; the word-at-a-time
+    unary scan), and a read behind the padded copy of the stream is silent on the hardware."""
+    subprocess.check_call(["make", "-s", "-j4", "-C", EMU, "asan"])
+    asan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"], text=True).strip()
+    _gpu_file_on_the_emulator(os.path.join(EMU, "libbvgraph_emu_asan.so"), "fwd", [os.path.join(ROOT, "tests", "test_gpu_derive.py"), "-k", DERIVE_UNDER_ASAN],
+                              LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1")
+
+
+@pytest.mark.parametrize("order,first", [("fwd", 0), ("rev", 10)])
+def test_randomised_offsets_derivation_on_the_emulator(emu_lib, order, first):
+    """tests/test_gpu_derive_fuzz.py, ten cases per lane order; the two orders run different cases."""
+    _gpu_file_on_the_emulator(emu_lib, order, [os.path.join(ROOT, "tests", "test_gpu_derive_fuzz.py")], BVG_DERIVE_FUZZ=str(first + 10), BVG_DERIVE_FUZZ_FROM=str(first))
+
+
 @pytest.mark.skipif(not os.environ.get("BVG_EMU_ASAN"), reason="opt-in (BVG_EMU_ASAN=1): the AddressSanitizer build of the emulated library takes ~4 minutes to compile")
 def test_compressor_input_check_under_address_sanitizer():
     """test_degenerate_adjacencies sends offsets that point a million elements past a three-element adjacency: enc_check_kernel must refuse

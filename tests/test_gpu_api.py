@@ -578,10 +578,11 @@ def test_offsets_are_derived_by_the_chunk_parallel_walk(W, tools, capfd, monkeyp
     for kw in (dict(window_size=0, max_ref_count=0, min_interval_length=0), dict(residual_coding=1, outdegree_coding=1, reference_coding=2, block_count_coding=5, block_coding=1),
                dict(residual_coding=7), dict(window_size=100, max_ref_count=20), dict(zeta_k=1, min_interval_length=2)):      # (Golomb residuals of a web graph are codes of thousands of bits: no walk derives those)
         s2 = tools.synth_store(200000, seed=5, params=W.default_params(**kw), threads=4)
+        capfd.readouterr()
         h = W.BVGraph.from_memory(s2.params, s2.graph, None)
+        assert "parallel walk ok" in capfd.readouterr().err, kw               # (per parameter set: a silent fall-back to the sequential walk is a failure)
         assert np.array_equal(h.offsets(), s2.offsets), kw
         h.close()
-    assert "parallel walk ok" in capfd.readouterr().err
     # one giant record in the middle of ordinary ones
     rng = np.random.default_rng(2)
     n = 400000
@@ -593,7 +594,9 @@ def test_offsets_are_derived_by_the_chunk_parallel_walk(W, tools, capfd, monkeyp
     off = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.uint64)
     s3 = tools.store((off, np.concatenate(lists).astype(np.int64)), W.default_params(), threads=4)
     assert int(np.diff(s3.offsets.astype(np.int64)).max()) > 10 * 32768       # the record spans more than ten chunks
+    capfd.readouterr()
     h = W.BVGraph.from_memory(s3.params, s3.graph, None)
+    assert "parallel walk ok" in capfd.readouterr().err
     assert np.array_equal(h.offsets(), s3.offsets)
     h.close()
     # a window beyond the ring of the parallel walk takes the sequential one

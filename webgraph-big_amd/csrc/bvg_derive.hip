@@ -13,8 +13,8 @@
 // within its own chunk (the codes are instantaneous and records are short); only chunks whose entry state changed are walked
 // again, so a region that cannot fall into step by itself (the inside of a record of millions of residuals) costs one
 // single-chunk launch per chunk.  A last pass numbers the record starts (prefix sum of the per-chunk counts) and writes the
-// offsets.  Anything odd in the final, exact walk (a code longer than 64 bits, a negative count, a reference beyond the window,
-// too few records) is reported, and the caller falls back to the sequential walk, whose error bits are the documented ones.
+// offsets.  Anything odd in the final, exact walk (a code other than unary longer than 64 bits, a negative count, a reference beyond
+// the window, too few records) is reported, and the caller falls back to the sequential walk, whose error bits are the documented ones.
 #include "bvg_kernels.h"
 #include "bvg_lds_codes.h"
 
@@ -31,6 +31,16 @@ constexpr int kMaxDeriveWindow = 127;          // outdegree ring per lane in LDS
 constexpr uint32_t kChunkBits = 32768;         // 4 KiB of stream per lane
 constexpr uint32_t kWarmChunks = 8;            // a guessed walk starts this many chunks before its own: by the time it enters it, it has almost always fallen into step
 constexpr uint32_t kCrawlBelow = 2048;         // rounds with at most this many chunks to walk give each chunk a workgroup (derive_crawl_kernel)
+
+// Both as test knobs (live under BVG_TEST_KNOBS only, bvg_kernels.h: knob()): BVG_DERIVE_WARM=0 starts every chunk from the raw guess, so
+// that detect / adopt settle hundreds of chunks on a small input; BVG_DERIVE_CRAWL=0 sends every later round to derive_round_kernel over the
+// list, a value above the chunk count every later round to derive_crawl_kernel.
+uint32_t knob_u32(const char* name, uint32_t dflt) {
+    const char* v = knob(name);
+    if (!v || !*v) return dflt;
+    char* e = nullptr; const unsigned long long x = strtoull(v, &e, 10);
+    return (e == v || x > 0x7FFFFFFFull) ? dflt : (uint32_t)x;
+}
 
 enum : uint32_t { F_OUTDEG = 0, F_REF, F_BCOUNT, F_BLOCK, F_ICOUNT, F_ILEFT, F_ILEN, F_RES };
 
@@ -62,7 +72,8 @@ struct BitBuf {
     }
 };
 
-// one code of the given coding from a 64-bit window: length (0 = longer than the window: impossible in a well-formed stream) and value
+// one code of the given coding from a 64-bit window: length (0 = longer than the window: unary codes are then read on by walk(), no other
+// code of a well-formed stream is) and value
 template <bool GEN>
 __device__ __forceinline__ uint32_t read_code(uint64_t w, int coding, uint32_t k, uint64_t& v) {
     if (!GEN) {                                                          // default codings: gamma / unary / zeta_k, computed side by side
@@ -78,7 +89,7 @@ __device__ __forceinline__ uint32_t read_code(uint64_t w, int coding, uint32_t k
 // (slot (j & M) * 64 of node j), cnt = nodes started so far (>= M + 1 when the walk begins).  emit(p) is called at every record start.
 template <bool GEN, typename Emit>
 __device__ __forceinline__ void walk(const uint8_t* g, WalkState& st, uint64_t end, uint32_t* ring, uint32_t M, uint32_t& cnt, int W, uint32_t minint, const Codings& cod,
-                                     unsigned& bad, Emit emit, const uint8_t* lens = nullptr, uint64_t lens_lo = 0) {
+                                     unsigned& bad, Emit emit, uint64_t total_bits, const uint8_t* lens = nullptr, uint64_t lens_lo = 0) {
     BitBuf bb; bb.init(g, st.pos);
     while (st.pos < end) {
         const uint32_t f = st.field;
@@ -91,7 +102,20 @@ __device__ __forceinline__ void walk(const uint8_t* g, WalkState& st, uint64_t e
         const uint64_t w = bb.peek(st.pos);
         const int coding = f == F_OUTDEG ? cod.outdegree : f == F_REF ? cod.reference : f == F_BCOUNT ? cod.block_count : f == F_BLOCK ? cod.block : f == F_RES ? cod.residual : BVG_GAMMA;
         uint64_t v;
-        uint32_t len = read_code<GEN>(w, coding, (uint32_t)cod.zeta_k, v);
+        uint64_t len;
+        if (coding == BVG_UNARY && w == 0) {
+            // a unary code of more than 64 bits (a reference beyond 63, a block count or a block of 64 and more in unary coding): count the
+            // zeros a word at a time, as the sequential walk does; a run of zeros to the end of the stream is no code.  A reference is
+            // followed no further than the window (a larger one is flagged anyway), which bounds what a GUESSED walk standing in a run of
+            // zero bytes reads per code under the default codings.  With block counts or blocks in unary coding there is no such bound:
+            // every guessed chunk inside a run of zeros may scan to the end of the run, quadratic in its length for a hostile stream (the
+            // time budget of the rounds is checked between launches only).
+            const uint64_t cap = f == F_REF ? (uint64_t)W : 0x7FFFFFFFull;
+            uint64_t p = st.pos, ww = 0;
+            while (ww == 0 && p + 64 < total_bits && p - st.pos <= cap) { p += 64; ww = bb.peek(p); }
+            if (ww) { v = (p - st.pos) + (uint64_t)__builtin_clzll(ww); len = v + 1; }
+            else { st.pos = p; len = 0; }                                 // (the buffer has moved on to p: go on from there)
+        } else len = read_code<GEN>(w, coding, (uint32_t)cod.zeta_k, v);
         if (len == 0) { bad |= 1u; len = 64; v = 0; }                     // (a guessed walk may read anything; the exact walk must not)
         st.pos += len;
         bool to_extras = false, to_res = false;
@@ -122,6 +146,7 @@ __device__ __forceinline__ void walk(const uint8_t* g, WalkState& st, uint64_t e
                 st.total += b; if (!(st.bi & 1u)) st.copied += b;
                 if (++st.bi == st.bc) {
                     if (!(st.bc & 1u)) st.copied += (int64_t)ring[((cnt - 1 - st.ref) & M) * 64] - st.total;      // BVG:1030
+                    if (st.copied < 0) bad |= 8u;                          // blocks that skip more than the referenced list has: the sequential walk's ERR_MALFORMED
                     st.extra = (int64_t)st.d - st.copied; to_extras = true;
                 }
                 break;
@@ -169,7 +194,7 @@ struct RoundArgs {
     const uint8_t* g; uint64_t total_bits; uint32_t nchunks; int W; uint32_t minint; Codings cod;
     const uint32_t* list; uint32_t nlist;
     WalkState* entry; uint32_t* entry_ring; WalkState* exit; uint32_t* exit_ring; uint32_t* counts;
-    uint32_t first_round;
+    uint32_t first_round, warm_chunks;
 };
 
 // The walk of chunk c from entry[c] (first round: from the guess, see below) to its end: exit[c], counts[c].
@@ -186,18 +211,19 @@ __device__ __forceinline__ void round_chunk(const RoundArgs& a, uint32_t c, uint
     unsigned bad = 0;
     uint32_t starts = 0;
     if (a.first_round && c > 0) {
-        // The guess: a record starts kWarmChunks chunks before mine (at bit 0, the truth, for the first ones) with an empty window.  A
+        // The guess: a record starts warm_chunks (kWarmChunks) chunks before mine (at bit 0, the truth, for the first ones) with an empty window.  A
         // walk that starts inside a record falls into step with the true boundaries after some thousands of codes (it has to END a
         // bogus record exactly on a true start, and then parse a window's worth of records right): walking that distance first makes
         // the state in which it enters its own chunk -- and with it almost every exit of the first round -- the true one.
-        st.pos = c > kWarmChunks ? lo - (uint64_t)kWarmChunks * kChunkBits : 0;
-        walk<GEN>(a.g, st, lo, ring, M, cnt, a.W, a.minint, a.cod, bad, [&](uint64_t) {});
+        st.pos = c > a.warm_chunks ? lo - (uint64_t)a.warm_chunks * kChunkBits : 0;
+        walk<GEN>(a.g, st, lo, ring, M, cnt, a.W, a.minint, a.cod, bad, [&](uint64_t) {}, a.total_bits);
         a.entry[c] = st;
         for (uint32_t j = 0; j < R; j++) my_ring[j] = ring[((cnt - 1 - j) & M) * 64];
         bad = 0;
     }
-    walk<GEN>(a.g, st, hi, ring, M, cnt, a.W, a.minint, a.cod, bad, [&](uint64_t) { starts++; }, lens, lo);
-    if (c + 1 == a.nchunks && st.field == F_OUTDEG) starts++;             // the position behind the last record counts as a start too (offsets[n])
+    walk<GEN>(a.g, st, hi, ring, M, cnt, a.W, a.minint, a.cod, bad, [&](uint64_t) { starts++; }, a.total_bits, lens, lo);
+    // (the position behind the last record, offsets[n], is not counted: counts[c] only feeds the prefix sum of the chunks before the next one,
+    // and derive_write_kernel writes offsets[n] from its own walk)
     a.counts[c] = starts;
     a.exit[c] = st;
     uint32_t* const xr = a.exit_ring + (size_t)c * R;
@@ -286,7 +312,7 @@ __global__ void __launch_bounds__(64) derive_write_kernel(const uint8_t* g, uint
     walk<GEN>(g, st, hi, ring, M, cnt, W, minint, cod, bad, [&](uint64_t p) {
         if (idx <= (uint64_t)n) { offsets[idx] = p; bad_before_n |= bad; }
         idx++;
-    });
+    }, total_bits);
     if (c + 1 == nchunks && st.field == F_OUTDEG) { if (idx <= (uint64_t)n) { offsets[idx] = st.pos; bad_before_n |= bad; } idx++; }
     if (idx <= (uint64_t)n) bad_before_n |= bad;                          // the chunk ends before record n does: everything it read counts
     if (bad_before_n) atomicOr(err, ERR_MALFORMED);
@@ -338,9 +364,10 @@ int derive_offsets_parallel(const uint8_t* graph, uint64_t nbytes, int64_t n, in
     const size_t lds = (size_t)Rp * 64 * 4;
     const uint32_t minint = (uint32_t)min_interval;
     uint32_t* const mis_list = lists; uint32_t* const walk_list = lists + nchunks;
+    const uint32_t warm_chunks = knob_u32("BVG_DERIVE_WARM", kWarmChunks), crawl_below = knob_u32("BVG_DERIVE_CRAWL", kCrawlBelow);
     auto launch_walk = [&](const uint32_t* list, uint32_t nlist, bool first) {
-        RoundArgs ra{graph, total_bits, nchunks, window, minint, cod, list, nlist, entry, entry_ring, exitst, exit_ring, counts, first ? 1u : 0u};
-        if (!first && nlist <= kCrawlBelow) {
+        RoundArgs ra{graph, total_bits, nchunks, window, minint, cod, list, nlist, entry, entry_ring, exitst, exit_ring, counts, first ? 1u : 0u, warm_chunks};
+        if (!first && nlist <= crawl_below) {
             const size_t lds2 = lds + kChunkBits + 64;
             if (gen) hipLaunchKernelGGL(derive_crawl_kernel<true>, dim3(nlist), dim3(kCrawlThreads), lds2, s, ra);
             else hipLaunchKernelGGL(derive_crawl_kernel<false>, dim3(nlist), dim3(kCrawlThreads), lds2, s, ra);
@@ -383,7 +410,7 @@ int derive_offsets_parallel(const uint8_t* graph, uint64_t nbytes, int64_t n, in
         hipLaunchKernelGGL(derive_adopt_kernel, dim3((h[0] + 255) / 256), dim3(256), 0, s, R, entry, entry_ring, exitst, exit_ring, mis_list, d_n, walk_list, d_n + 2);
         uint32_t nw = 0;
         if (hipMemcpyAsync(&nw, d_n + 2, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return -2;
-        if (dbg_on() && (rounds < 24 || (rounds & (rounds - 1)) == 0)) fprintf(stderr, "[bvg] derive round %d: %u of %u chunks do not enter where their predecessor left (the first: %u), %u walked again\n", rounds, h[0], nchunks, h[1], nw);
+        if (dbg_on() && (rounds < 24 || (rounds & (rounds - 1)) == 0)) fprintf(stderr, "[bvg] derive round %d: %u of %u chunks do not enter where their predecessor left (the first: %u), %u walked again by the %s kernel (warm-up %u chunks)\n", rounds, h[0], nchunks, h[1], nw, nw <= crawl_below ? "crawl" : "list", warm_chunks);
         if (nw == 0) return -3;                                          // (cannot happen: the first mismatching chunk is always walked)
         launch_walk(walk_list, nw, false);
         rounds++;

@@ -1,5 +1,5 @@
 // bvg_derive_seq.hip — the offsets index from a bare .graph by ONE wavefront walking the records in order: the fall-back of the
-// chunk-parallel derivation (bvg_derive.hip) for windows > 127, codes longer than 64 bits and streams the parallel walk finds odd.
+// chunk-parallel derivation (bvg_derive.hip) for windows > 127 and streams the parallel walk finds odd.
 // (Until round 4 this lived beside the experimental streaming kernel in bvg_stream.hip; that kernel is now experimental/bvg_stream.hip.)
 #include "bvg_kernels.h"
 #include "bvg_lds_codes.h"
@@ -68,7 +68,9 @@ __global__ void __launch_bounds__(64) derive_offsets_kernel(const uint8_t* graph
             uint32_t ref = 0;
             if (window > 0) {
                 if (!code(cod.reference, 0, v)) { err = ERR_OVERRUN; break; }
-                if (v > (uint64_t)window || (int64_t)v > x) { err = ERR_REF_RANGE; break; }
+                // (a reference before node 0 is NOT refused: the reference's sequential iterator reads outdegree 0 from its fresh window there,
+                // BVG:1018 and :1030 -- dring is zeroed, and slot (x - ref) & (kRingBig - 1) of a negative x - ref is written by no node <= x)
+                if (v > (uint64_t)window) { err = ERR_REF_RANGE; break; }
                 ref = (uint32_t)v;
             }
             int64_t extra = d;
@@ -103,6 +105,10 @@ __global__ void __launch_bounds__(64) derive_offsets_kernel(const uint8_t* graph
         if ((x & 63) == 63 || x == n - 1) {                                  // 64 offsets at a time, coalesced
             const int64_t x0 = x & ~63ll;
             if (x0 + lane <= x) offsets[x0 + lane] = mine;
+            // dring is written and read by every lane alike; the barrier keeps the lanes within 64 nodes of each other, so that no lane reuses a slot
+            // (node x + 2048) that another still reads as node x - ref (kRingBig - kMaxWindowBig = 64).  A wavefront runs in step anyway; the host
+            // emulator (tests/emu) does not: through thousands of empty records, which need no refill of the stream ring, its lanes drifted apart.
+            __syncthreads();
         }
     }
     if (lane == 0) { offsets[n] = pos; if (err) atomicOr(errp, err); }
