@@ -258,6 +258,59 @@ int bvg_bfs_get(bvg_bfs* v, int64_t* marker, int64_t* queue, uint64_t queue_cap,
 int bvg_bfs_get_dev(bvg_bfs* v, void* d_marker, void* d_queue, uint64_t queue_cap, void* d_cutpoints, uint64_t cut_cap, void* d_dist);
 int bvg_bfs_counters(const bvg_bfs* v, uint64_t* out);
 
+/* ---- HyperBall (algo/HyperBall.java; non-systolic iterations, counters in device memory) ----
+ * One HyperLogLog counter of m = 2^log2m registers per node, log2m in [4, 12] (below: BVG_E_ARG, above: BVG_E_UNSUPPORTED).  An iteration
+ * makes every counter the register-wise maximum of itself and of the counters of the node's successors that the previous iteration
+ * modified (self-loops skipped), counts it, and adds the count to a new term of the neighbourhood function (HyperBall.java:777-919 with
+ * systolic == local == external == false, :1000-1182); with BVG_HB_SUM_OF_DISTANCES / BVG_HB_HARMONIC a node whose counter changed by
+ * delta = count after - count before > 0 in iteration k (from 0) adds (float)(delta (k + 1)) / (float)(delta / (k + 1)) to its float32
+ * sum of distances / sum of inverse distances.  After the pass the term is raised to the previous one if it is smaller (:1165).
+ * THE HASH IS THIS LIBRARY'S (the reference takes its counters from a library outside its tree): register contents are not those of
+ * the Java implementation, the algorithm and the estimator are.  Node v under `seed` goes to
+ *     x = mix64(v + (seed + 1) * 0x9E3779B97F4A7C15)      mix64(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *     j = x & (m - 1)                                                z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31
+ *     r = ctz((x >> log2m) | 1 << (64 - log2m)) + 1
+ *     reg[j] = max(reg[j], r)                             (all arithmetic modulo 2^64; r <= 65 - log2m: one byte per register)
+ * count = alpha m^2 / sum_j 2^-reg[j], alpha = 0.673, 0.697, 0.709 for m = 16, 32, 64 and 0.7213 / (1 + 1.079 / m) above; when some register
+ * is 0 and the count is below 2.5 m it is m ln(m / zeroes) instead.  The sum is exact before its one rounding, so counts do not depend
+ * on the order of anything; the terms of the neighbourhood function are added in a fixed order (no floating-point atomics).
+ * The object holds a bvg_copy() flyweight of g (own stream and workspaces): g stays usable and may be closed first.  Requires
+ * node_base == 0 (BVG_E_ARG).  Device memory: 2 nodes m bytes of counters (one byte per register), nodes / 4 of modified bits, 4 nodes
+ * per centrality array, and one arc-bounded batch of the decode (as bvg_components); BVG_E_NOMEM leaves g usable.
+ * bvg_hyperball_create: allocates; nothing is initialised yet.  bvg_hyperball_init: init(seed) (:580-607) -- node i added to counter i,
+ *   neighbourhood function = [nodes], iteration = -1, every counter modified, centralities 0.  bvg_hyperball_iterate: one iteration;
+ *   before init: BVG_E_STATE.  bvg_hyperball_run: run(upperBound, threshold) (:1222-1239) with the seed of create or of the last init:
+ *   init, then at most min(upper_bound, nodes) iterations (upper_bound < 0: no bound), stopping after one that modified nothing, or, from
+ *   the fifth on, after one whose relative increment is below 1 + threshold (-1: never).
+ * bvg_hyperball_info: iteration (-1 after init), modified() of the last iteration (nodes after init), the last relative increment, the
+ *   length of the neighbourhood function; any pointer may be NULL.  bvg_hyperball_neighbourhood_function: out[cap >= length].
+ * bvg_hyperball_registers: counters [from, to) as (to - from) m bytes, register j of counter x at out[(x - from) m + j].
+ * bvg_hyperball_counts / _dev (device buffer): the counts of counters [from, to) (double).
+ * bvg_hyperball_centrality / _dev: float[nodes] by the formulas of HyperBall.main (:1349-1388) -- the sum of distances d; the harmonic
+ *   centrality (sum of inverse distances); closeness d == 0 ? 0 : 1 / d; Lin d == 0 ? 1 : count^2 / d; Nieminen count^2 - d; reachable =
+ *   count.  The first, closeness, Lin and Nieminen need BVG_HB_SUM_OF_DISTANCES, harmonic needs BVG_HB_HARMONIC: BVG_E_STATE otherwise.
+ * bvg_hyperball_relative_standard_deviation: beta / sqrt(m), beta = 1.106, 1.070, 1.054, 1.046 for log2m 4..7 and 1.04 above.
+ * Malformed streams report the decode's status (a successor outside [0, nodes): BVG_E_EOF, never used as an index); after an error of an
+ * iteration the object needs bvg_hyperball_init (BVG_E_STATE until then).  NULL or invalid arguments: BVG_E_ARG, no device touched.
+ * Not built: systolic / local iterations (they need the transpose as a graph), external counters, discount functions, node weights. */
+#define BVG_HB_SUM_OF_DISTANCES 1u
+#define BVG_HB_HARMONIC 2u
+enum { BVG_HB_WHICH_SUM_OF_DISTANCES = 0, BVG_HB_WHICH_HARMONIC = 1, BVG_HB_WHICH_CLOSENESS = 2, BVG_HB_WHICH_LIN = 3, BVG_HB_WHICH_NIEMINEN = 4, BVG_HB_WHICH_REACHABLE = 5 };
+typedef struct bvg_hyperball bvg_hyperball;
+int bvg_hyperball_create(bvg_graph* g, int log2m, uint32_t flags, uint64_t seed, bvg_hyperball** out);
+void bvg_hyperball_close(bvg_hyperball* h);
+int bvg_hyperball_init(bvg_hyperball* h, uint64_t seed);
+int bvg_hyperball_iterate(bvg_hyperball* h);
+int bvg_hyperball_run(bvg_hyperball* h, int64_t upper_bound, double threshold);
+int bvg_hyperball_info(const bvg_hyperball* h, int64_t* iteration, uint64_t* modified, double* relative_increment, uint64_t* nf_len);
+int bvg_hyperball_neighbourhood_function(const bvg_hyperball* h, double* out, uint64_t cap);
+int bvg_hyperball_registers(bvg_hyperball* h, int64_t from, int64_t to, uint8_t* out);
+int bvg_hyperball_counts(bvg_hyperball* h, int64_t from, int64_t to, double* out);
+int bvg_hyperball_counts_dev(bvg_hyperball* h, int64_t from, int64_t to, void* d_out);
+int bvg_hyperball_centrality(bvg_hyperball* h, int which, float* out);
+int bvg_hyperball_centrality_dev(bvg_hyperball* h, int which, void* d_out);
+double bvg_hyperball_relative_standard_deviation(int log2m);
+
 /* ---- arc labels stored as a bit stream (labelling/BitStreamArcLabelledImmutableGraph.java) ----
  * basename.labels holds, node after node, the labels of the node's arcs in successor order (:75-84); basename.labeloffsets the
  * gamma-coded bit lengths of those runs after a leading gamma(0) (store(), :655-680).  The node iterator reads `outdegree`

@@ -13,4 +13,5 @@ from .bvgraph import (BVGraph, NodeIterator, LazyLongIterator, BVGraphError, Ill
                       BitStreamArcLabelledImmutableGraph, LabelledArcIterator, parse_label_spec, LABEL_GAMMA_INT, LABEL_FIXED_INT, LABEL_FIXED_INT_LIST, LABEL_FIXED_LONG_LIST,
                       scan_multi, mosaic, BALANCE_NODES, BALANCE_BITS, BALANCE_ARCS, store,
                       CC_SORT_BY_SIZE, ComponentsResult, store_components, load_components, components_main,
-                      BFS_PARENT, BFS_COUNTERS, BreadthFirstVisit)
+                      BFS_PARENT, BFS_COUNTERS, BreadthFirstVisit,
+                      HB_SUM_OF_DISTANCES, HB_HARMONIC, HyperBall, hyperball_main, store_floats, load_floats)

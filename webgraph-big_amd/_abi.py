@@ -49,6 +49,23 @@ def bfs_signatures():
             "bvg_bfs_visit_all": [vp], "bvg_bfs_info": [vp, C.POINTER(i64), C.POINTER(u64), C.POINTER(u64)],
             "bvg_bfs_get": [vp, vp, vp, u64, vp, u64, vp], "bvg_bfs_get_dev": [vp, vp, vp, u64, vp, u64, vp], "bvg_bfs_counters": [vp, vp]}
 
+
+# bvg_hyperball_create flags and the `which` of bvg_hyperball_centrality (BVG_HB_*, BVG_HB_WHICH_*)
+HB_SUM_OF_DISTANCES_FLAG, HB_HARMONIC_FLAG = 1, 2
+HB_WHICH = {"sum_of_distances": 0, "harmonic": 1, "closeness": 2, "lin": 3, "nieminen": 4, "reachable": 5}
+
+
+def hyperball_signatures():
+    """argtypes of the bvg_hyperball_* entry points, by name."""
+    vp, i64, u64, pp, dbl = C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(C.c_void_p), C.c_double
+    return {"bvg_hyperball_create": [vp, C.c_int, C.c_uint32, u64, pp], "bvg_hyperball_close": [vp], "bvg_hyperball_init": [vp, u64],
+            "bvg_hyperball_iterate": [vp], "bvg_hyperball_run": [vp, i64, dbl],
+            "bvg_hyperball_info": [vp, C.POINTER(i64), C.POINTER(u64), C.POINTER(dbl), C.POINTER(u64)],
+            "bvg_hyperball_neighbourhood_function": [vp, vp, u64], "bvg_hyperball_registers": [vp, i64, i64, vp],
+            "bvg_hyperball_counts": [vp, i64, i64, vp], "bvg_hyperball_counts_dev": [vp, i64, i64, vp],
+            "bvg_hyperball_centrality": [vp, C.c_int, vp], "bvg_hyperball_centrality_dev": [vp, C.c_int, vp],
+            "bvg_hyperball_relative_standard_deviation": [C.c_int]}
+
 OK, E_ARG, E_STATE, E_UNSUPPORTED, E_IO, E_EOF, E_NOMEM, E_HIP, E_CAPACITY = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 

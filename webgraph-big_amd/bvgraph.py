@@ -182,6 +182,21 @@ def _bfs_fns():
     return L
 
 
+def _hyperball_fns():
+    """The bvg_hyperball_* entry points, bound on first use (as _bfs_fns)."""
+    L = lib()
+    if getattr(L, "_hb_bound", False):
+        return L
+    for name, args in _abi.hyperball_signatures().items():
+        if not hasattr(L, name):
+            raise UnsupportedOperationException(_abi.E_UNSUPPORTED, name + " is not in this build of the library")
+        getattr(L, name).argtypes = args
+    L.bvg_hyperball_close.restype = None
+    L.bvg_hyperball_relative_standard_deviation.restype = C.c_double
+    L._hb_bound = True
+    return L
+
+
 def store(adj, params=None, chunk_nodes=0, device=0):
     """BVGraph.store on the device (bvg_store): adj = (adj_off uint64[n+1], succ int64[m]) or a list of sorted lists.
     Returns (graph uint8[], offsets uint64[n+1]); byte for byte what the reference's compressor writes.
@@ -804,6 +819,12 @@ class BVGraph:
 
     breadthFirstVisit = breadth_first_visit
 
+    def hyperball(self, log2m, seed=0, sum_of_distances=False, harmonic=False):
+        """HyperBall (algo/HyperBall.java, non-systolic) with its counters on the device: see HyperBall."""
+        return HyperBall(self, log2m, seed, sum_of_distances, harmonic)
+
+    hyperBall = hyperball
+
     def build_index(self, frm=0, to=None):
         """Builds the residual skip index (and validates the blocks) of nodes [frm, to) now (bvg_build_index) instead of inside
         the first scan; returns (entries, bytes) of the graph's index afterwards."""
@@ -946,6 +967,208 @@ class BreadthFirstVisit:
         out = np.zeros(len(BFS_COUNTERS), dtype=np.uint64)
         _check(self._L.bvg_bfs_counters(self._v, out.ctypes.data), "counters")
         return dict(zip(BFS_COUNTERS, (int(x) for x in out)))
+
+
+HB_SUM_OF_DISTANCES, HB_HARMONIC = 1, 2
+
+
+class HyperBall:
+    """What HyperBall holds (one HyperLogLog counter of 2^log2m registers per node, the neighbourhood function, the float32 sums of
+    distances and of inverse distances when asked for; HyperBall.java:580-607, 777-919, 1000-1239), kept on the device between
+    iterations (bvg_hyperball_*).  Iterations are the reference's standard (non-systolic, in-memory) ones.  The hash behind the
+    counters is this library's (include/bvgraph_hip.h), so registers are not those of the Java implementation; the algorithm and the
+    estimator are.  The object holds its own flyweight of the graph.  Usable as a context manager."""
+
+    def __init__(self, graph, log2m, seed=0, sum_of_distances=False, harmonic=False):
+        self._L = _hyperball_fns()
+        self._h = C.c_void_p()
+        self._n = graph.num_nodes()
+        self.log2m, self.m = int(log2m), 1 << max(int(log2m), 0)
+        flags = (HB_SUM_OF_DISTANCES if sum_of_distances else 0) | (HB_HARMONIC if harmonic else 0)
+        _check(self._L.bvg_hyperball_create(graph._h, int(log2m), flags, int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(self._h)), "hyperball(log2m=%d)" % log2m)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.bvg_hyperball_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def init(self, seed=0):
+        _check(self._L.bvg_hyperball_init(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF), "init")
+
+    def iterate(self):
+        _check(self._L.bvg_hyperball_iterate(self._h), "iterate")
+
+    def run(self, upper_bound=-1, threshold=-1.0):
+        """run(upperBound, threshold): init with the object's seed, then iterate until nothing is modified, upper_bound (negative: none)
+        iterations are done, or (threshold != -1) the relative increment falls below 1 + threshold after the fifth iteration."""
+        _check(self._L.bvg_hyperball_run(self._h, int(upper_bound), float(threshold)), "run")
+
+    def _info(self):
+        it, mod, rel, k = C.c_int64(), C.c_uint64(), C.c_double(), C.c_uint64()
+        _check(self._L.bvg_hyperball_info(self._h, C.byref(it), C.byref(mod), C.byref(rel), C.byref(k)), "info")
+        return int(it.value), int(mod.value), float(rel.value), int(k.value)
+
+    @property
+    def iteration(self):
+        return self._info()[0]
+
+    def modified(self):
+        return self._info()[1]
+
+    @property
+    def relative_increment(self):
+        return self._info()[2]
+
+    @property
+    def neighbourhood_function(self):
+        k = self._info()[3]
+        out = np.empty(k, dtype=np.float64)
+        if k:
+            _check(self._L.bvg_hyperball_neighbourhood_function(self._h, out.ctypes.data, k), "neighbourhood_function")
+        return out
+
+    neighbourhoodFunction = neighbourhood_function
+
+    def registers(self, frm=0, to=None):
+        """The registers of counters [frm, to): uint8[to - frm, m]."""
+        to = self._n if to is None else to
+        out = np.empty((max(to - frm, 0), self.m), dtype=np.uint8)
+        _check(self._L.bvg_hyperball_registers(self._h, frm, to, out.ctypes.data if out.size else None), "registers(%d,%d)" % (frm, to))
+        return out
+
+    def counts(self, frm=0, to=None):
+        to = self._n if to is None else to
+        out = np.empty(max(to - frm, 0), dtype=np.float64)
+        _check(self._L.bvg_hyperball_counts(self._h, frm, to, out.ctypes.data if out.size else None), "counts(%d,%d)" % (frm, to))
+        return out
+
+    def count(self, x):
+        return float(self.counts(x, x + 1)[0])
+
+    def counts_dev(self, tensor, frm=0, to=None):
+        """bvg_hyperball_counts_dev into a contiguous float64 CUDA tensor of at least to - frm elements."""
+        to = self._n if to is None else to
+        _check(self._L.bvg_hyperball_counts_dev(self._h, frm, to, tensor.data_ptr()), "counts_dev")
+
+    def _centrality(self, which):
+        out = np.empty(self._n, dtype=np.float32)
+        _check(self._L.bvg_hyperball_centrality(self._h, _abi.HB_WHICH[which], out.ctypes.data if self._n else None), which)
+        return out
+
+    def centrality_dev(self, which, tensor):
+        """bvg_hyperball_centrality_dev into a contiguous float32 CUDA tensor of numNodes() elements; which: a key of _abi.HB_WHICH."""
+        _check(self._L.bvg_hyperball_centrality_dev(self._h, _abi.HB_WHICH[which], tensor.data_ptr()), which)
+
+    def sum_of_distances(self):
+        return self._centrality("sum_of_distances")
+
+    def harmonic_centrality(self):
+        return self._centrality("harmonic")
+
+    def closeness(self):
+        return self._centrality("closeness")
+
+    def lin(self):
+        return self._centrality("lin")
+
+    def nieminen(self):
+        return self._centrality("nieminen")
+
+    def reachable(self):
+        return self._centrality("reachable")
+
+    sumOfDistances, sumOfInverseDistances = sum_of_distances, harmonic_centrality
+
+    @staticmethod
+    def relative_standard_deviation(log2m):
+        return float(_hyperball_fns().bvg_hyperball_relative_standard_deviation(int(log2m)))
+
+
+def _plain_decimal(x):
+    """BigDecimal.valueOf(double).toPlainString(): the shortest decimal that reads back as x, never in scientific notation."""
+    from decimal import Decimal
+    return format(Decimal(repr(float(x))), "f")
+
+
+def store_floats(values, path):
+    """BinIO.storeFloats / DataOutputStream.writeFloat: big-endian float32, no header."""
+    np.asarray(values, dtype=">f4").tofile(path)
+    return path
+
+
+def load_floats(path):
+    return np.fromfile(path, dtype=">f4").astype(np.float32)
+
+
+def hyperball_arg_parser():
+    """The command line of HyperBall.main, for what is built: the option letters are the reference's."""
+    import argparse
+    ap = argparse.ArgumentParser(prog="hyperball", add_help=False, description="HyperBall on the device: neighbourhood function and geometric centralities of a BVGraph.")
+    ap.add_argument("--help", action="help", help="show this message (-h is the reference's harmonic-centrality option)")
+    ap.add_argument("-l", "--log2m", type=int, default=12, help="the logarithm of the number of registers per counter (4..12; default 12, the largest supported)")
+    ap.add_argument("-u", "--upper-bound", type=int, default=-1, help="an upper bound to the number of iterations")
+    ap.add_argument("-t", "--threshold", default="-1", help="stop when the relative increment falls below 1 + threshold (-1: only at stabilisation)")
+    ap.add_argument("-n", "--neighbourhood-function", help="store the neighbourhood function in text format")
+    ap.add_argument("-d", "--sum-of-distances", help="store the sum of distances from each node (big-endian floats)")
+    ap.add_argument("-h", "--harmonic-centrality", help="store the harmonic centrality of each node (big-endian floats)")
+    ap.add_argument("-c", "--closeness-centrality", help="store the closeness centrality of each node (big-endian floats)")
+    ap.add_argument("-L", "--lin-centrality", help="store the Lin centrality of each node (big-endian floats)")
+    ap.add_argument("-N", "--nieminen-centrality", help="store the Nieminen centrality of each node (big-endian floats)")
+    ap.add_argument("-r", "--reachable", help="store the number of nodes reachable from each node (big-endian floats)")
+    ap.add_argument("-S", "--seed", type=int, default=0, help="the random seed")
+    ap.add_argument("-e", "--external", action="store_true", help="(not built: counters live in device memory)")
+    ap.add_argument("-z", "--discounted-gain-centrality", action="append", help="(not built)")
+    ap.add_argument("-Z", dest="big_z", action="append", help="(not built)")
+    ap.add_argument("--device", type=int, default=0, help="the GPU to run on")
+    ap.add_argument("basename", help="the basename of the graph")
+    ap.add_argument("basenamet", nargs="?", default=None, help="(not built: the transpose, for systolic iterations)")
+    return ap
+
+
+def hyperball_main(argv=None):
+    """HyperBall.main for the standard iterations: loads basename, runs, writes the files asked for.  Returns the HyperBall's
+    neighbourhood function."""
+    ap = hyperball_arg_parser()
+    args = ap.parse_args(argv)
+    try:
+        threshold = float(args.threshold)
+    except ValueError:
+        ap.error("-t is the threshold here, and %r is not a number: a transpose basename (systolic iterations) is not supported" % args.threshold)
+    if args.basenamet is not None:
+        ap.error("a transpose basename (systolic iterations) is not supported: give the graph's basename only")
+    if args.external:
+        ap.error("-e (external counters) is not supported: the counters live in device memory")
+    if args.discounted_gain_centrality or args.big_z:
+        ap.error("-z / -Z (discounted gain centralities) are not supported")
+    need_sod = bool(args.sum_of_distances or args.closeness_centrality or args.lin_centrality or args.nieminen_centrality)
+    g = BVGraph.load(args.basename, device=args.device)
+    try:
+        with g.hyperball(args.log2m, seed=args.seed, sum_of_distances=need_sod, harmonic=bool(args.harmonic_centrality)) as hb:
+            hb.run(args.upper_bound, threshold)
+            nf = hb.neighbourhood_function
+            if args.neighbourhood_function:
+                with open(args.neighbourhood_function, "w") as f:
+                    for x in nf:
+                        f.write(_plain_decimal(x) + "\n")
+            for path, get in ((args.sum_of_distances, hb.sum_of_distances), (args.harmonic_centrality, hb.harmonic_centrality), (args.closeness_centrality, hb.closeness),
+                              (args.lin_centrality, hb.lin), (args.nieminen_centrality, hb.nieminen), (args.reachable, hb.reachable)):
+                if path:
+                    store_floats(get(), path)
+    finally:
+        g.close()
+    return nf
 
 
 class ComponentsResult:

@@ -180,6 +180,8 @@ public:
     }
     // breadth-first visits on the device (algo/ParallelBreadthFirstVisit.java): the class is below
     inline class ParallelBreadthFirstVisit breadthFirstVisit(bool parent = false);
+    // HyperBall on the device (algo/HyperBall.java, standard iterations): the class is below
+    inline class HyperBall hyperBall(int log2m, uint64_t seed = 0, bool sumOfDistances = false, bool harmonic = false);
     NodeIterator nodeIterator(int64_t from = 0) { return NodeIterator(shared_from_this(), from, INT64_MAX); }   // BVGraph.java:1257
     std::vector<NodeIterator> splitNodeIterators(int howMany) {                            // ImmutableGraph.java:405-436
         std::vector<NodeIterator> v; const int64_t n = p_.nodes, m = (n + howMany - 1) / howMany;
@@ -227,6 +229,52 @@ public:
     int64_t nodeAtMaxDistance() const { const std::vector<int64_t> q = queue(); if (q.empty()) throw std::out_of_range("nodeAtMaxDistance: empty queue"); return q.back(); }
 };
 inline ParallelBreadthFirstVisit BVGraph::breadthFirstVisit(bool parent) { return ParallelBreadthFirstVisit(*this, parent); }
+
+// HyperBall (algo/HyperBall.java, non-systolic in-memory iterations) over bvg_hyperball_*: the counters live on the device between
+// iterations.  The hash behind the counters is this library's (include/bvgraph_hip.h); the algorithm and the estimator are the reference's.
+class HyperBall {
+    bvg_hyperball* h_ = nullptr; int64_t n_ = 0; int log2m_ = 0;
+    std::vector<float> centrality(int which, const char* what) const { std::vector<float> out((size_t)n_); check(bvg_hyperball_centrality(h_, which, n_ ? out.data() : nullptr), what); return out; }
+public:
+    HyperBall(BVGraph& g, int log2m, uint64_t seed, bool sumOfDistances, bool harmonic) : n_(g.numNodes()), log2m_(log2m) {
+        check(bvg_hyperball_create(g.handle(), log2m, (sumOfDistances ? BVG_HB_SUM_OF_DISTANCES : 0u) | (harmonic ? BVG_HB_HARMONIC : 0u), seed, &h_), "hyperball_create");
+    }
+    HyperBall(HyperBall&& o) noexcept : h_(o.h_), n_(o.n_), log2m_(o.log2m_) { o.h_ = nullptr; }
+    HyperBall(const HyperBall&) = delete;
+    HyperBall& operator=(const HyperBall&) = delete;
+    ~HyperBall() { bvg_hyperball_close(h_); }
+    void init(uint64_t seed = 0) { check(bvg_hyperball_init(h_, seed), "hyperball_init"); }
+    void iterate() { check(bvg_hyperball_iterate(h_), "hyperball_iterate"); }
+    void run(int64_t upperBound = -1, double threshold = -1) { check(bvg_hyperball_run(h_, upperBound, threshold), "hyperball_run"); }
+    int64_t iteration() const { int64_t i = 0; check(bvg_hyperball_info(h_, &i, nullptr, nullptr, nullptr), "hyperball_info"); return i; }
+    int64_t modified() const { uint64_t m = 0; check(bvg_hyperball_info(h_, nullptr, &m, nullptr, nullptr), "hyperball_info"); return (int64_t)m; }
+    double relativeIncrement() const { double r = 0; check(bvg_hyperball_info(h_, nullptr, nullptr, &r, nullptr), "hyperball_info"); return r; }
+    std::vector<double> neighbourhoodFunction() const {
+        uint64_t k = 0; check(bvg_hyperball_info(h_, nullptr, nullptr, nullptr, &k), "hyperball_info");
+        std::vector<double> out((size_t)k);
+        if (k) check(bvg_hyperball_neighbourhood_function(h_, out.data(), k), "hyperball_neighbourhood_function");
+        return out;
+    }
+    std::vector<uint8_t> registers(int64_t from, int64_t to) const {
+        std::vector<uint8_t> out((size_t)(to - from) << log2m_);
+        check(bvg_hyperball_registers(h_, from, to, out.empty() ? nullptr : out.data()), "hyperball_registers");
+        return out;
+    }
+    std::vector<double> counts(int64_t from, int64_t to) const {
+        std::vector<double> out((size_t)(to - from));
+        check(bvg_hyperball_counts(h_, from, to, out.empty() ? nullptr : out.data()), "hyperball_counts");
+        return out;
+    }
+    double count(int64_t x) const { return counts(x, x + 1)[0]; }
+    std::vector<float> sumOfDistances() const { return centrality(BVG_HB_WHICH_SUM_OF_DISTANCES, "sumOfDistances"); }
+    std::vector<float> sumOfInverseDistances() const { return centrality(BVG_HB_WHICH_HARMONIC, "sumOfInverseDistances"); }
+    std::vector<float> closeness() const { return centrality(BVG_HB_WHICH_CLOSENESS, "closeness"); }
+    std::vector<float> lin() const { return centrality(BVG_HB_WHICH_LIN, "lin"); }
+    std::vector<float> nieminen() const { return centrality(BVG_HB_WHICH_NIEMINEN, "nieminen"); }
+    std::vector<float> reachable() const { return centrality(BVG_HB_WHICH_REACHABLE, "reachable"); }
+    static double relativeStandardDeviation(int log2m) { return bvg_hyperball_relative_standard_deviation(log2m); }
+};
+inline HyperBall BVGraph::hyperBall(int log2m, uint64_t seed, bool sumOfDistances, bool harmonic) { return HyperBall(*this, log2m, seed, sumOfDistances, harmonic); }
 
 inline NodeIterator::NodeIterator(std::shared_ptr<BVGraph> g, int64_t from, int64_t upperBound, int64_t batchNodes)
     : g_(std::move(g)), from_(from), curr_(from - 1), batch_(batchNodes) {
