@@ -9,6 +9,8 @@ import os
 import numpy as np
 import pytest
 
+import sweep_cases
+
 GOLDEN_CNR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "cnr-2000")
 
 pytestmark = pytest.mark.gpu
@@ -393,6 +395,19 @@ def test_star_longer_than_the_budget(W, tools, monkeypatch, route):
     g = open_graph(W, tools, off, adj)
     for start in (7, 100, 3):
         check_visit(g, off, adj, start)
+
+
+# long runs of nodes without successors at the start, in the middle and at the end: node ranges the sweep's batch plan leaves out
+@pytest.mark.parametrize("budget", ["1", "97"])
+def test_empty_runs_under_tiny_budgets(W, tools, monkeypatch, budget):
+    monkeypatch.setenv("BVG_BFS_ROUTE", "sweep"); monkeypatch.setenv("BVG_BFS_BATCH_ARCS", budget)
+    off, adj = sweep_cases.empty_runs_graph()
+    assert np.diff(off.astype(np.int64)).max() > int(budget)                   # the longest list exceeds the budget
+    g = open_graph(W, tools, off, adj)
+    _, _, dist, _, c = check_visit(g, off, adj, sweep_cases.LONG_NODE)
+    assert c["frontier_levels"] == 0 and c["sweep_batches"] > c["sweep_levels"] > 2
+    assert all((dist[lo:hi] > 0).any() for lo, hi in sweep_cases.EMPTY)         # nodes of every empty run are reached
+    check_visit(g, off, adj, sweep_cases.NODES - 1, both_modes=False)          # from a node without successors
 
 
 @pytest.mark.parametrize("depth", [1, 5, 12])

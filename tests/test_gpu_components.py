@@ -12,6 +12,8 @@ import sys
 import numpy as np
 import pytest
 
+import sweep_cases
+
 GOLDEN_CNR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "cnr-2000")
 
 pytestmark = pytest.mark.gpu
@@ -180,6 +182,17 @@ def test_batch_boundaries_do_not_change_the_result(W, tools, monkeypatch, budget
     src, dst = arcs_of(off, adj)
     k, comp, sizes = check(g, n, src, dst)
     assert sizes.max() > 97                                                    # a component that spans several batches of 97 arcs
+
+
+# 4b. long runs of nodes without successors at the start, in the middle and at the end: node ranges the batch plan leaves out
+@pytest.mark.parametrize("budget", ["1", "97"])
+def test_empty_runs_under_tiny_budgets(W, tools, monkeypatch, budget):
+    monkeypatch.setenv("BVG_CC_BATCH_ARCS", budget)
+    off, adj = sweep_cases.empty_runs_graph()
+    assert np.diff(off.astype(np.int64)).max() > int(budget)                   # the longest list exceeds the budget
+    st = tools.store((off, adj), threads=2)
+    g = W.BVGraph.from_memory(st.params, st.graph, st.offsets)
+    check(g, len(off) - 1, *arcs_of(off, adj))
 
 
 # 5. sortBySize and a sizes buffer that is too small

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import hyperball_model as M
+import sweep_cases
 from conftest import CNR
 
 pytestmark = pytest.mark.gpu
@@ -132,6 +133,17 @@ def test_tiny_batches(W, tools, monkeypatch, budget):
     assert np.diff(off.astype(np.int64)).max() > int(budget)                   # a list that is a batch of its own
     g = open_graph(W, tools, off, adj)
     lockstep(g, off, adj, 6, seed=5, max_iterations=5)
+
+
+# long runs of nodes without successors at the start, in the middle and at the end: node ranges the batch plan leaves out, whose counters
+# are carried over and counted all the same
+@pytest.mark.parametrize("budget", ["1", "97"])
+def test_empty_runs_under_tiny_batches(W, tools, monkeypatch, budget):
+    monkeypatch.setenv("BVG_HB_BATCH_ARCS", budget)
+    off, adj = sweep_cases.empty_runs_graph()
+    assert np.diff(off.astype(np.int64)).max() > int(budget)                   # the longest list exceeds the budget
+    g = open_graph(W, tools, off, adj)
+    lockstep(g, off, adj, 5, max_iterations=4)
 
 
 @pytest.mark.parametrize("tuning", [dict(force_wide=True), dict(force_slow=True), dict(no_index=1)], ids=["force_wide", "force_slow", "no_index"])

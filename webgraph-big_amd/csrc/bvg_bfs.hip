@@ -8,7 +8,7 @@
 //   expand     the successor lists of level d, by one of two routes chosen per level:
 //                frontier  the body of bvg_successors_batch with the requests read from the queue (batch_degrees / batch_halos / batch_decode,
 //                          bvg_api.hip), in pieces of at most the arc budget;
-//                sweep     the whole graph decoded in arc-bounded node ranges as bvg_components does (plan_batches, run_decode), of which the
+//                sweep     the whole graph decoded in arc-bounded node ranges (SweepPlan, bvg_plan.hip), of which the
 //                          mark kernel takes the lists whose source has dist == d.  Random access to a large share of the graph costs more than
 //                          decoding all of it in order.
 //   mark       one wavefront per 64 lists: the lengths of the lists to expand are prefix-summed across the wavefront (LDS), then the lanes walk
@@ -47,19 +47,16 @@ namespace bvg {
 
 namespace {
 
-// Every kernel strides over its elements: a launch holds fewer than 2^32 work-items, and graphs may have more nodes than that.
-#define BFS_FOR(I, N) for (int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; I < (int64_t)(N); I += (int64_t)gridDim.x * blockDim.x)
-
 template <typename T> __device__ __forceinline__ constexpr T none() { return (T)~(T)0; }   // the marker's -1 (never a node: the 32-bit kernels stop at 2^32 - 256 nodes)
 
 enum : int { kCtlBad = 0, kCtlCount = 1, kCtlFirst = 2, kCtlWords = 4 };   // control words (unsigned long long) the host reads back
 
 template <typename T> __global__ void bfs_fill_kernel(T* marker, T* cand, int32_t* dist, int64_t n) {
-    BFS_FOR(x, n) { marker[x] = none<T>(); if (cand) cand[x] = none<T>(); dist[x] = -1; }
+    BVG_FOR(x, n) { marker[x] = none<T>(); if (cand) cand[x] = none<T>(); dist[x] = -1; }
 }
 
 __global__ void bfs_reset_dist_kernel(const int64_t* queue, uint64_t count, int32_t* dist) {
-    BFS_FOR(i, count) dist[queue[i]] = -1;
+    BVG_FOR(i, count) dist[queue[i]] = -1;
 }
 
 template <typename T> __global__ void bfs_seed_kernel(int64_t start, T mark, T* marker, int32_t* dist, int64_t* queue) {
@@ -125,17 +122,17 @@ __global__ void __launch_bounds__(256) bfs_mark_kernel(const uint64_t* cum, cons
 
 // parent mode, over the new level: the smallest candidate becomes the parent, and the candidate is reset for the levels to come
 template <typename T> __global__ void bfs_adopt_kernel(const int64_t* level, uint64_t count, T* marker, T* cand) {
-    BFS_FOR(i, count) { const int64_t y = level[i]; marker[y] = cand[y]; cand[y] = none<T>(); }
+    BVG_FOR(i, count) { const int64_t y = level[i]; marker[y] = cand[y]; cand[y] = none<T>(); }
 }
 
 template <typename T> __global__ void bfs_widen_kernel(const T* marker, int64_t n, int64_t* out) {
-    BFS_FOR(x, n) { const T m = marker[x]; out[x] = m == none<T>() ? -1 : (int64_t)m; }
+    BVG_FOR(x, n) { const T m = marker[x]; out[x] = m == none<T>() ? -1 : (int64_t)m; }
 }
 
 // ---- visit_all: what the nodes of a chunk [a, a + cnt) need
 // need[i] = 1: node a + i has successors; nodes of outdegree 1 are listed (any order) for the check of their one successor
 __global__ void bfs_classify_kernel(const int32_t* deg, int64_t a, int64_t cnt, uint8_t* need, int64_t* ones, unsigned long long* n_ones) {
-    BFS_FOR(i, cnt) {
+    BVG_FOR(i, cnt) {
         const int32_t dg = deg[i];
         need[i] = dg > 0 ? 1 : 0;
         if (dg == 1) ones[atomicAdd(n_ones, 1ull)] = a + i;
@@ -143,7 +140,7 @@ __global__ void bfs_classify_kernel(const int32_t* deg, int64_t a, int64_t cnt, 
 }
 // a node whose only successor is itself needs no expansion (ParallelBreadthFirstVisit.java:309-317)
 __global__ void bfs_loops_kernel(const int64_t* ones, int64_t count, const uint64_t* cum, const int64_t* succ, int64_t a, uint8_t* need) {
-    BFS_FOR(i, count) if (cum[i + 1] == cum[i] + 1 && succ[cum[i]] == ones[i]) need[ones[i] - a] = 0;
+    BVG_FOR(i, count) if (cum[i + 1] == cum[i] + 1 && succ[cum[i]] == ones[i]) need[ones[i] - a] = 0;
 }
 // the first node of [from, to) that is unmarked and needs an expansion (*first: `to` when there is none).  Lanes hold increasing ids, so the
 // lowest set lane of a wavefront is its minimum: one atomic per wavefront, and none once a smaller node is known (a stale *first is larger:
@@ -158,19 +155,17 @@ template <typename T> __global__ void __launch_bounds__(256) bfs_find_kernel(con
 }
 template <typename T> __global__ void bfs_flag_kernel(const T* marker, int64_t from, int64_t to, const unsigned long long* first, int32_t* flag) {
     const int64_t stop = (int64_t)*first < to ? (int64_t)*first : to;
-    BFS_FOR(i, to - from) flag[i] = (from + i < stop && marker[from + i] == none<T>()) ? 1 : 0;
+    BVG_FOR(i, to - from) flag[i] = (from + i < stop && marker[from + i] == none<T>()) ? 1 : 0;
 }
 // the unmarked nodes before *first get their marker: each is a visit of its own, so round numbers go up by one per node
 template <typename T, bool PARENT> __global__ void bfs_number_kernel(T* marker, int64_t from, int64_t to, const int32_t* flag, const uint64_t* rank, int64_t round) {
-    BFS_FOR(i, to - from) if (flag[i]) marker[from + i] = PARENT ? (T)(from + i) : (T)(round + 1 + (int64_t)rank[i]);
+    BVG_FOR(i, to - from) if (flag[i]) marker[from + i] = PARENT ? (T)(from + i) : (T)(round + 1 + (int64_t)rank[i]);
 }
 
 struct InLevel {
     const int32_t* dist; int32_t level;
     __device__ bool operator()(const int64_t& x) const { return dist[x] == level; }
 };
-
-inline unsigned grid(int64_t n, int64_t per) { const int64_t b = (n + per - 1) / per; return (unsigned)(b < 1 ? 1 : (b > (1 << 18) ? (1 << 18) : b)); }   // (the kernels stride)
 
 }  // namespace
 
@@ -183,7 +178,8 @@ using bvghost::DevBuf;
 
 namespace {
 
-constexpr uint64_t kMaxBudgetArcs = 1ull << 30;    // 8 GiB of successors per batch
+constexpr uint64_t kMaxBudgetArcs = 1ull << 30;    // 8 GiB of successors per batch.  Below kMaxBatchArcs: the object keeps two such buffers between visits (succ for the
+                                                   // frontier route, sw_ws for the sweep), each with Grow's quarter of slack
 constexpr uint64_t kSmallCap = 1ull << 16;         // winners up to this many are sorted; more: the node range is compacted
 constexpr int64_t kPiece = 1ll << 24;              // requests of one frontier piece (its node-side arrays: ~100 bytes each)
 constexpr int64_t kChunk = 1ll << 20;              // nodes of one visit_all search chunk
@@ -213,7 +209,7 @@ struct bvg_bfs {
     int force_route = 0;                           // 1 frontier, 2 sweep
     uint64_t per = 0, small_cap = kSmallCap, switch_den = kSwitchDen;
     // the graph in arc-bounded node ranges (sweep route), planned at the first need
-    bool planned = false; std::vector<Batch> batches; uint64_t arcs = 0, longest = 0; bool arcs_known = false;
+    bool planned = false; bvghost::SweepPlan sweep; uint64_t arcs = 0; bool arcs_known = false;
     Grow fr_bufs, succ, sw_ws, prim, chunk_ws, wide_out;
     // visit_all's chunk
     int64_t ch_a = -1, ch_b = -1;
@@ -234,25 +230,15 @@ template <typename T> int clear_t(bvg_bfs* v) {
     return 0;
 }
 
-int budget(bvg_bfs* v) {
-    if (v->per) return 0;
-    size_t fr = 0, tot = 0;
-    HIPCHK(hipMemGetInfo(&fr, &tot));
-    const uint64_t head = (256ull << 20) + fr / 16 + (uint64_t)v->n * 12;                // (as bvg_components: the decode's own workspaces, a batch's node-side arrays)
-    uint64_t per = fr > head ? (fr - head) / 2 / 8 : 1;
-    if (per > kMaxBudgetArcs) per = kMaxBudgetArcs;
-    v->per = per < 1 ? 1 : per;
-    return 0;
-}
+// the arc budget, at the first visit and before any plan: the frontier route needs it without a sweep (the knob was read when the object was created)
+int budget(bvg_bfs* v) { return v->per ? 0 : arc_budget(v->n, kMaxBudgetArcs, nullptr, &v->per); }
 
 int ensure_plan(bvg_bfs* v) {
     if (v->planned) return 0;
-    bvg_graph* g = v->g;
     int rc = budget(v); if (rc) return rc;
-    // the residual skip index first, for the whole graph (as bvg_components does: small batches would not build it)
-    if (g->tun.no_index != 1 && v->n >= 4096) (void)bvg_build_index(g, 0, v->n, nullptr, nullptr);
-    rc = plan_batches(g, v->per, v->batches, &v->arcs, &v->longest); if (rc) return rc;
-    v->arcs_known = true; v->planned = true;
+    index_first(v->g);
+    rc = v->sweep.build(v->g, v->per); if (rc) return rc;
+    v->arcs = v->sweep.arcs; v->arcs_known = true; v->planned = true;
     return 0;
 }
 
@@ -328,19 +314,13 @@ template <typename T> int expand_frontier(bvg_bfs* v, uint64_t lo, uint64_t hi, 
 template <typename T> int expand_sweep(bvg_bfs* v, int32_t d) {
     bvg_graph* g = v->g;
     int rc = ensure_plan(v); if (rc) return rc;
-    if (v->batches.empty()) return 0;
-    int64_t maxn = 0; for (const Batch& b : v->batches) maxn = std::max(maxn, b.hi - b.lo);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_cum = 0, o_tmp = o_cum + al(((size_t)maxn + 1) * 8), o_deg = o_tmp + al(scan_tmp_elems(maxn) * 8), o_succ = o_deg + al((size_t)maxn * 4);
-    rc = v->sw_ws.ensure(o_succ + (size_t)std::max<uint64_t>(v->longest, 1) * 8); if (rc) return rc;
-    char* const w = (char*)v->sw_ws.b.p;
-    uint64_t* const b_cum = (uint64_t*)(w + o_cum); int32_t* const b_deg = (int32_t*)(w + o_deg); int64_t* const b_succ = (int64_t*)(w + o_succ);
-    for (const Batch& b : v->batches) {
-        const int64_t cnt = b.hi - b.lo;
-        outdegrees_of(g, b.lo, b.hi, b_deg);
-        launch_exclusive_scan(b_deg, b_cum, cnt, (uint64_t*)(w + o_tmp), g->stream);
-        rc = run_decode(g, b.lo, b.hi, true, b_cum, b_succ, nullptr, nullptr); if (rc) return rc;
-        launch_mark<T>(v, true, b_cum, nullptr, b.lo, cnt, b_succ, d);
+    bvghost::SweepPlan& sp = v->sweep;
+    if (sp.batches.empty()) return 0;
+    rc = v->sw_ws.ensure(sp.bytes); if (rc) return rc;
+    sp.bind(v->sw_ws.b.p);
+    for (const Batch& b : sp.batches) {
+        rc = sp.decode(g, b); if (rc) return rc;
+        launch_mark<T>(v, true, sp.cum(), nullptr, b.lo, b.hi - b.lo, sp.succ(), d);
         HIPCHK(hipGetLastError());
         v->counters[kSweepBatches]++;
     }
@@ -493,14 +473,6 @@ template <typename T> int visit_all_t(bvg_bfs* v) {
         }
     }
     return 0;
-}
-
-template <typename F> int on_device(bvg_bfs* v, F&& f) {
-    if (!v) return BVG_E_ARG;
-    return bvghost::guarded([&]() -> int {
-        HIPCHK(hipSetDevice(v->g->sh->device));
-        return f();
-    });
 }
 
 int clear_any(bvg_bfs* v) { return v->wide ? clear_t<uint64_t>(v) : clear_t<uint32_t>(v); }

@@ -65,11 +65,8 @@ template <typename T> __device__ __forceinline__ void unite(T* parent, T a, T b)
     }
 }
 
-// Every kernel strides over its elements: a launch holds fewer than 2^32 work-items, and graphs may have more nodes than that.
-#define CC_FOR(I, N) for (int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; I < (int64_t)(N); I += (int64_t)gridDim.x * blockDim.x)
-
 template <typename T> __global__ void cc_init_kernel(T* parent, int64_t n) {
-    CC_FOR(x, n) parent[x] = (T)x;
+    BVG_FOR(x, n) parent[x] = (T)x;
 }
 
 // One wavefront per 64 consecutive nodes of the batch [lo, lo + cnt) (four per workgroup): the root of every source is found once per
@@ -112,7 +109,7 @@ template <typename T> __global__ void __launch_bounds__(256) cc_hook_kernel(cons
 // parent[x] = root of x; flag[x] = 1 for the roots.  Only thread x writes parent[x], and with the root, so the label kernel reads
 // every node's root in one load; the other threads' walks through x see the old or the new value, both ancestors
 template <typename T> __global__ void cc_compress_kernel(T* parent, int64_t n, int32_t* flag) {
-    CC_FOR(x, n) {
+    BVG_FOR(x, n) {
         const T r = find_root<T, false>(parent, (T)x);
         st_parent(parent + x, r);
         flag[x] = r == (T)x ? 1 : 0;
@@ -120,7 +117,7 @@ template <typename T> __global__ void cc_compress_kernel(T* parent, int64_t n, i
 }
 
 template <typename T> __global__ void cc_label_kernel(const T* parent, int64_t n, const uint64_t* rank, int64_t* comp) {
-    CC_FOR(x, n) comp[x] = (int64_t)rank[parent[x]];
+    BVG_FOR(x, n) comp[x] = (int64_t)rank[parent[x]];
 }
 
 // sizes[comp[x]] += 1: consecutive nodes mostly share a label, so each wavefront adds one count per run of equal labels among its
@@ -145,7 +142,7 @@ __global__ void __launch_bounds__(256) cc_sizes_kernel(const int64_t* comp, int6
 
 // sort key of component i: n - size (ascending = size descending); values: the old index (increasing, so a stable sort orders ties by it)
 __global__ void cc_sort_keys_kernel(const unsigned long long* sizes, uint64_t count, uint64_t n, uint64_t* keys, uint64_t* idx) {
-    CC_FOR(i, count) {
+    BVG_FOR(i, count) {
         keys[i] = n - (uint64_t)sizes[i];
         idx[i] = (uint64_t)i;
     }
@@ -153,17 +150,15 @@ __global__ void cc_sort_keys_kernel(const unsigned long long* sizes, uint64_t co
 
 // new index of old component order[j] is j; sizes in the new order
 __global__ void cc_invert_kernel(const uint64_t* keys_sorted, const uint64_t* order, uint64_t count, uint64_t n, uint64_t* newidx, unsigned long long* sizes) {
-    CC_FOR(j, count) {
+    BVG_FOR(j, count) {
         newidx[order[j]] = (uint64_t)j;
         sizes[j] = (unsigned long long)(n - keys_sorted[j]);
     }
 }
 
 __global__ void cc_remap_kernel(int64_t* comp, int64_t n, const uint64_t* newidx) {
-    CC_FOR(x, n) comp[x] = (int64_t)newidx[comp[x]];
+    BVG_FOR(x, n) comp[x] = (int64_t)newidx[comp[x]];
 }
-
-inline unsigned grid(int64_t n, int64_t per) { const int64_t b = (n + per - 1) / per; return (unsigned)(b < 1 ? 1 : (b > (1 << 18) ? (1 << 18) : b)); }   // (the kernels stride)
 
 }  // namespace
 
@@ -173,66 +168,44 @@ namespace {
 
 using bvghost::DevBuf;
 
-constexpr uint64_t kMaxBatchArcs = 1ull << 32;     // 32 GiB of successors: the per-batch overhead (a plan lookup, two syncs) is already negligible
-
 template <typename T> int components_t(bvg_graph* g, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components, bool dev) {
     Shared* sh = g->sh; const int64_t n = sh->p.nodes;
     const bool dbgt = dbg_on();
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto tA = now();
-    // the residual skip index first, for the whole graph (a no-op when it exists): batches below a quarter of the graph would not build
-    // it and would all run on the checking kernels.  A build that fails leaves the batches index-less, nothing worse.
-    if (g->tun.no_index != 1 && n >= 4096) (void)bvg_build_index(g, 0, n, nullptr, nullptr);
+    Stopwatch sw;
+    index_first(g);
     DevBuf parent;
     if (parent.alloc((size_t)n * sizeof(T))) return BVG_E_NOMEM;
     T* const d_parent = (T*)parent.p;
     hipLaunchKernelGGL((cc_init_kernel<T>), dim3(grid(n, 256)), dim3(256), 0, g->stream, d_parent, n);
-    // batch budget: half of what is free once the parent array is there, less headroom for the decode's own workspaces; at most kMaxBatchArcs
-    uint64_t per = 0;
-    if (const char* k = knob("BVG_CC_BATCH_ARCS")) { const long long v = atoll(k); if (v > 0) per = (uint64_t)v; }
-    if (!per) {
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        const uint64_t head = (256ull << 20) + fr / 16 + (uint64_t)n * 12;            // (+ the node-side arrays of a batch and the planning pass)
-        per = fr > head ? (fr - head) / 2 / 8 : 1;
-        if (per > kMaxBatchArcs) per = kMaxBatchArcs;
-        if (per < 1) per = 1;
-    }
-    std::vector<Batch> batches; uint64_t arcs = 0, longest = 0;
-    int rc = plan_batches(g, per, batches, &arcs, &longest); if (rc) return rc;
-    const auto tB = now();
+    uint64_t per = 0;                                                       // (of what is free once the parent array is there)
+    int rc = arc_budget(n, kMaxBatchArcs, "BVG_CC_BATCH_ARCS", &per); if (rc) return rc;
+    SweepPlan sp;
+    rc = sp.build(g, per); if (rc) return rc;
+    const double t_plan = sw.lap();
     double t_dec = 0, t_hook = 0;
     DevBuf d_bad;
     if (d_bad.alloc(256)) return BVG_E_NOMEM;
     HIPCHK(hipMemsetAsync(d_bad.p, 0, sizeof(unsigned), g->stream));
-    if (!batches.empty()) {
-        int64_t maxn = 0; for (const Batch& b : batches) maxn = std::max(maxn, b.hi - b.lo);
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t o_cum = 0, o_tmp = o_cum + al(((size_t)maxn + 1) * 8), o_deg = o_tmp + al(scan_tmp_elems(maxn) * 8), o_succ = o_deg + al((size_t)maxn * 4);
-        DevBuf ws;
-        if (ws.alloc(o_succ + (size_t)std::max<uint64_t>(longest, 1) * 8)) return BVG_E_NOMEM;   // parent array + the largest batch: does not fit
-        char* const w = (char*)ws.p;
-        uint64_t* const b_cum = (uint64_t*)(w + o_cum); int32_t* const b_deg = (int32_t*)(w + o_deg); int64_t* const b_succ = (int64_t*)(w + o_succ);
-        for (const Batch& b : batches) {
+    if (!sp.batches.empty()) {
+        DevBuf ws;                                                          // (this scope: gone before the numbering pass, which needs the memory)
+        if (ws.alloc(sp.bytes)) return BVG_E_NOMEM;                         // parent array + the largest batch: does not fit
+        sp.bind(ws.p);
+        for (const Batch& b : sp.batches) {
             const int64_t cnt = b.hi - b.lo;
-            const auto t0 = now();
-            outdegrees_of(g, b.lo, b.hi, b_deg);
-            launch_exclusive_scan(b_deg, b_cum, cnt, (uint64_t*)(w + o_tmp), g->stream);
-            rc = run_decode(g, b.lo, b.hi, true, b_cum, b_succ, nullptr, nullptr); if (rc) return rc;
-            if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); }
-            const auto t1 = now();
-            hipLaunchKernelGGL((cc_hook_kernel<T>), dim3(grid(cnt, 256)), dim3(256), 0, g->stream, (const uint64_t*)b_cum, b.lo, cnt, (const int64_t*)b_succ, n, d_parent,
+            sw.lap();
+            rc = sp.decode(g, b); if (rc) return rc;
+            if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); t_dec += sw.lap(); }
+            hipLaunchKernelGGL((cc_hook_kernel<T>), dim3(grid(cnt, 256)), dim3(256), 0, g->stream, (const uint64_t*)sp.cum(), b.lo, cnt, (const int64_t*)sp.succ(), n, d_parent,
                                (unsigned*)d_bad.p);
             HIPCHK(hipGetLastError());
-            if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); t_dec += ms(t0, t1); t_hook += ms(t1, now()); }
+            if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); t_hook += sw.lap(); }
         }
     }
     unsigned bad = 0;
     HIPCHK(hipMemcpyAsync(&bad, d_bad.p, sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     if (bad) return BVG_E_EOF;                                              // a successor outside [0, n): malformed stream
-    const auto tC = now();
+    sw.lap();
     // compress + number (the batch buffer is gone by now)
     DevBuf flag, rank, tmp, dcomp;
     if (flag.alloc((size_t)n * 4) || rank.alloc(((size_t)n + 1) * 8) || tmp.alloc(scan_tmp_elems(n) * 8)) return BVG_E_NOMEM;
@@ -278,9 +251,8 @@ template <typename T> int components_t(bvg_graph* g, uint32_t flags, int64_t* co
     }
     if (!dev) HIPCHK(hipMemcpy(comp, d_comp, (size_t)n * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipGetLastError());
-    const auto tD = now();
     if (dbgt) fprintf(stderr, "[bvg] components: plan %.1f ms (%zu batches of <= %llu arcs, %llu arcs), decode %.1f ms, hook %.1f ms, finish %.1f ms (%llu components)\n",
-                      ms(tA, tB), batches.size(), (unsigned long long)per, (unsigned long long)arcs, t_dec, t_hook, ms(tC, tD), (unsigned long long)count);
+                      t_plan, sp.batches.size(), (unsigned long long)per, (unsigned long long)sp.arcs, t_dec, t_hook, sw.lap(), (unsigned long long)count);
     return cap_ok ? 0 : BVG_E_CAPACITY;
 }
 

@@ -1,6 +1,7 @@
 // bvg_host.h — what the host-side translation units of libbvgraph_hip.so share (round 6: csrc/bvg_api.hip split into plan / index / tier scheduler / C entry points):
 // the handle, the block plan, the residual skip index and the functions that cross the files.  Internal: nothing here is part of the C ABI (include/bvgraph_hip.h).
-//   bvg_plan.hip    parameters, handles, the block plan (node blocks of ~4 KiB of stream, halos), the packed offsets, opening a graph
+//   bvg_plan.hip    parameters, handles, the block plan (node blocks of ~4 KiB of stream, halos), the packed offsets, opening a graph; arc-bounded batches and
+//                   the one sweep over the whole graph that the analytics share (below: "arc-bounded batches")
 //   bvg_index.hip   (kernels) + bvg_index_host.hip: the residual skip index -- granularity, the build (counting pass, dense walk, validating pass), basename.bvgidx on disk
 //   bvg_sched.hip   run_decode: the tier scheduler (tier 0 + LDS classes + giants launched side by side, fail-over, what a scan learns about its blocks)
 //   bvg_api.hip     the extern "C" entry points
@@ -232,12 +233,52 @@ struct BatchPlan { const uint64_t* d_first; const uint32_t* d_halo; const uint64
 int run_decode(bvg_graph* g, int64_t from, int64_t to, bool materialise, const uint64_t* d_cum, int64_t* d_succ, int32_t* d_outdeg,
                bvg_scan_result* res, const BatchPlan* batch = nullptr, const std::shared_ptr<Plan>* use_plan = nullptr);
 
-// ---- bvg_plan.hip: the graph (or any list of lists with prefix sums on the device) cut into arc-bounded ranges (bvg_components, bvg_bfs_visit)
+// ---- what the kernels of the analytics (bvg_components, bvg_bfs, bvg_hyperball) are launched with
+// Every such kernel strides over its elements: a launch holds fewer than 2^32 work-items, and graphs may have more nodes than that.
+#define BVG_FOR(I, N) for (int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; I < (int64_t)(N); I += (int64_t)gridDim.x * blockDim.x)
+inline unsigned grid(int64_t n, int64_t per) { const int64_t b = (n + per - 1) / per; return (unsigned)(b < 1 ? 1 : (b > (1 << 18) ? (1 << 18) : b)); }   // (the kernels stride)
+
+// an entry point of an object that holds a bvg_copy() flyweight in ->g (bvg_bfs, bvg_hyperball): the guard, and the graph's device made current
+template <typename O, typename F> static int on_device(O* o, F&& f) {
+    if (!o) return BVG_E_ARG;
+    return guarded([&]() -> int {
+        HIPCHK(hipSetDevice(o->g->sh->device));
+        return f();
+    });
+}
+
+// wall clock of the BVG_DEBUG splits (decode / consume): the milliseconds since the last lap
+struct Stopwatch {
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    double lap() { const auto u = std::chrono::steady_clock::now(); const double ms = std::chrono::duration<double, std::milli>(u - t).count(); t = u; return ms; }
+};
+
+// ---- bvg_plan.hip: arc-bounded batches.  The graph (or any list of lists with prefix sums on the device) cut into ranges of at most `per` arcs, and
+// the sweep over the whole compressed graph in such ranges that bvg_components, the sweep route of bvg_bfs_visit and bvg_hyperball_iterate
+// share: index_first, arc_budget, then a SweepPlan and per batch SweepPlan::decode followed by the caller's own kernel.  The caller owns the
+// workspace (components: per call, freed before the numbering pass; bfs: grown on demand; hyperball: once per plan) and the order of these
+// steps against its own allocations, which decides how much memory a batch takes on a full card.
 constexpr int64_t kMaxBatchNodes = 1ll << 30;      // node ranges of a launch stay well below 2^32 work-items
+constexpr uint64_t kMaxBatchArcs = 1ull << 32;     // 32 GiB of successors: the per-batch overhead (a plan lookup, two syncs) is already negligible
 struct Batch { int64_t lo, hi; uint64_t arcs; };
 void outdegrees_of(bvg_graph* g, int64_t from, int64_t to, int32_t* out);
 int cut_batches(bvg_graph* g, const uint64_t* d_cum, int64_t n, uint64_t arcs, uint64_t per, std::vector<Batch>& out, uint64_t* longest_out);
 int plan_batches(bvg_graph* g, uint64_t per, std::vector<Batch>& out, uint64_t* arcs_out, uint64_t* longest_out);
+void index_first(bvg_graph* g);
+int arc_budget(int64_t n, uint64_t cap, const char* knob_name, uint64_t* per);
+struct SweepPlan {
+    std::vector<Batch> batches; uint64_t arcs = 0, longest = 0; int64_t maxn = 0;   // maxn: nodes of the widest batch
+    bool every_node = false;
+    size_t o_tmp = 0, o_deg = 0, o_extra = 0, o_succ = 0, bytes = 0;                 // the workspace: cum (at 0), scan tmp, deg, extra, `longest` successors
+    char* base = nullptr;
+    int build(bvg_graph* g, uint64_t per, bool every_node = false);
+    void layout(size_t extra_bytes);
+    void bind(void* ws) { base = (char*)ws; }
+    uint64_t* cum() const { return (uint64_t*)base; }
+    int64_t* succ() const { return (int64_t*)(base + o_succ); }
+    void* extra() const { return base + o_extra; }
+    int decode(bvg_graph* g, const Batch& b) const;
+};
 
 // ---- bvg_api.hip: what bvg_successors_batch and the frontier route of bvg_bfs_visit share (described there)
 int decode_range_impl(bvg_graph* g, int64_t from, int64_t to, int32_t* outdeg, int64_t* succ, uint64_t cap, uint64_t* n_succ, bool dev, bool narrow = false);

@@ -3,8 +3,7 @@
 // One HyperLogLog counter of m = 2^log2m registers per node; iteration k makes counter x the register-wise maximum of itself and of the
 // counters of its successors, so after it counter x estimates the nodes within distance k + 1 of x.  The sum of the estimates is a term of the
 // neighbourhood function; the increments of a node's estimate, weighted by the distance, are its sum of distances and its harmonic centrality.
-// The graph stays compressed: an iteration decodes it in arc-bounded node ranges as bvg_components does (plan_batches, run_decode with
-// materialise = true) and consumes each batch at once.
+// The graph stays compressed: an iteration decodes it in arc-bounded node ranges (SweepPlan, bvg_plan.hip) and consumes each batch at once.
 //
 // Hash (ours: the reference's comes from a library that is not part of it; include/bvgraph_hip.h has the definition):
 //   x = mix64(v + (seed + 1) * 0x9E3779B97F4A7C15), j = x & (m - 1), r = ctz((x >> log2m) | 1 << (64 - log2m)) + 1, reg[j] = max(reg[j], r).
@@ -49,8 +48,6 @@
 namespace bvg {
 
 namespace {
-
-#define HB_FOR(I, N) for (int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; I < (int64_t)(N); I += (int64_t)gridDim.x * blockDim.x)
 
 enum : int { kCtlBad = 0, kCtlModified = 1, kCtlPassed = 2, kCtlWords = 4 };   // control words (unsigned long long) the host reads back
 constexpr uint64_t kLong = 256;                    // lists of this many arcs and more are walked by the whole wavefront
@@ -118,7 +115,7 @@ template <int LOG2M> __device__ __forceinline__ double count_regs(const Regs<Sha
 template <int LOG2M> __global__ void hb_init_kernel(uint8_t* cur, int64_t n, uint64_t seed) {
     using S = Shape<LOG2M>;
     constexpr int PIECES = S::M / 16;
-    HB_FOR(i, n * PIECES) {
+    BVG_FOR(i, n * PIECES) {
         const int64_t x = i / PIECES; const unsigned piece = (unsigned)(i % PIECES);
         const uint64_t h = hb_mix64((uint64_t)x + (seed + 1) * 0x9E3779B97F4A7C15ull);
         const unsigned j = (unsigned)(h & (uint64_t)(S::M - 1));
@@ -283,7 +280,7 @@ __global__ void __launch_bounds__(256) hb_reduce_kernel(const double* partial, i
 }
 
 __global__ void hb_fill_mod_kernel(uint32_t* mod, int64_t n, int64_t words) {
-    HB_FOR(i, words) {
+    BVG_FOR(i, words) {
         const int64_t first = i * 32;
         mod[i] = first + 32 <= n ? 0xFFFFFFFFu : first >= n ? 0u : (1u << (unsigned)(n - first)) - 1u;
     }
@@ -291,7 +288,7 @@ __global__ void hb_fill_mod_kernel(uint32_t* mod, int64_t n, int64_t words) {
 
 // the estimates of counters [from, to): one thread per counter (not a hot path)
 __global__ void hb_counts_kernel(const uint8_t* cur, int64_t from, int64_t to, int log2m, double alpha_mm, double* out) {
-    HB_FOR(i, to - from) {
+    BVG_FOR(i, to - from) {
         const uint32_t* p = (const uint32_t*)(cur + ((uint64_t)(from + i) << log2m));
         uint64_t hi = 0, lo = 0; uint32_t zeros = 0;
         for (int k = 0; k < (1 << log2m) / 4; k++) tally4(p[k], hi, lo, zeros);
@@ -301,7 +298,7 @@ __global__ void hb_counts_kernel(const uint8_t* cur, int64_t from, int64_t to, i
 
 // the centralities of HyperBall.main (HyperBall.java:1349-1388)
 __global__ void hb_centrality_kernel(int which, const float* sod, const float* sid, const double* count, int64_t n, float* out) {
-    HB_FOR(x, n) {
+    BVG_FOR(x, n) {
         float r = 0;
         switch (which) {
             case BVG_HB_WHICH_SUM_OF_DISTANCES: r = sod[x]; break;
@@ -315,8 +312,6 @@ __global__ void hb_centrality_kernel(int which, const float* sod, const float* s
     }
 }
 
-inline unsigned grid(int64_t n, int64_t per) { const int64_t b = (n + per - 1) / per; return (unsigned)(b < 1 ? 1 : (b > (1 << 18) ? (1 << 18) : b)); }   // (the kernels stride)
-
 }  // namespace
 
 }  // namespace bvg
@@ -325,8 +320,6 @@ using bvghost::Batch;
 using bvghost::DevBuf;
 
 namespace {
-
-constexpr uint64_t kMaxBatchArcs = 1ull << 32;     // as bvg_components
 
 double alpha_mm_of(int log2m) {
     const double m = (double)(1 << log2m);
@@ -345,57 +338,26 @@ struct bvg_hyperball {
     bool inited = false;
     int64_t iteration = -1; uint64_t modified = 0; double relative_increment = 0;
     std::vector<double> nf;
-    // the graph in arc-bounded node ranges, planned at the first iteration
-    bool planned = false; std::vector<Batch> batches; uint64_t per = 0, arcs = 0, longest = 0; int64_t maxn = 0;
-    size_t o_cum = 0, o_tmp = 0, o_deg = 0, o_part = 0, o_succ = 0;
+    // the graph in arc-bounded node ranges, planned at the first iteration; its extra region: one partial sum per wavefront of the widest batch
+    bool planned = false; bvghost::SweepPlan sweep;
     ~bvg_hyperball() { if (g) { (void)hipSetDevice(g->sh->device); bvg_close(g); } }
 };
 
 namespace {
 
-template <typename F> int on_device(bvg_hyperball* h, F&& f) {
-    if (!h) return BVG_E_ARG;
-    return bvghost::guarded([&]() -> int {
-        HIPCHK(hipSetDevice(h->g->sh->device));
-        return f();
-    });
-}
-
 int ensure_plan(bvg_hyperball* h) {
     if (h->planned) return 0;
     bvg_graph* g = h->g;
-    // the residual skip index first, for the whole graph (as bvg_components does: small batches would not build it)
-    if (g->tun.no_index != 1 && h->n >= 4096) (void)bvg_build_index(g, 0, h->n, nullptr, nullptr);
-    uint64_t per = 0;
-    if (const char* k = knob("BVG_HB_BATCH_ARCS")) { const long long v = atoll(k); if (v > 0) per = (uint64_t)v; }
-    if (!per) {                                                                  // half of what is free with the counters in place, as bvg_components
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        const uint64_t head = (256ull << 20) + fr / 16 + (uint64_t)h->n * 12;
-        per = fr > head ? (fr - head) / 2 / 8 : 1;
-        if (per > kMaxBatchArcs) per = kMaxBatchArcs;
-        if (per < 1) per = 1;
-    }
-    h->per = per;
-    std::vector<Batch> batches;
-    int rc = plan_batches(g, per, batches, &h->arcs, &h->longest); if (rc) return rc;
-    // every node has a counter to carry over and to count, its list empty or not: the node ranges the plan leaves out (they hold no arcs)
-    // become batches of their own, which are not decoded
-    {
-        std::vector<Batch> all;
-        int64_t at = 0;
-        auto gap = [&](int64_t to) { for (; at < to; at = std::min(to, at + bvghost::kMaxBatchNodes)) all.push_back(Batch{at, std::min(to, at + bvghost::kMaxBatchNodes), 0}); };
-        for (const Batch& b : batches) { gap(b.lo); all.push_back(b); at = b.hi; }
-        gap(h->n);
-        batches.swap(all);
-    }
-    int64_t maxn = 0; for (const Batch& b : batches) maxn = std::max(maxn, b.hi - b.lo);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    h->o_cum = 0; h->o_tmp = h->o_cum + al(((size_t)maxn + 1) * 8); h->o_deg = h->o_tmp + al(scan_tmp_elems(maxn) * 8);
-    h->o_part = h->o_deg + al((size_t)maxn * 4); h->o_succ = h->o_part + al(((size_t)maxn / 64 + 1) * 8);
+    index_first(g);
+    uint64_t per = 0;                                                            // (of what is free with the counters in place)
+    int rc = arc_budget(h->n, kMaxBatchArcs, "BVG_HB_BATCH_ARCS", &per); if (rc) return rc;
+    bvghost::SweepPlan sp;
+    rc = sp.build(g, per, true); if (rc) return rc;                              // every node has a counter to carry over and to count, its list empty or not
+    sp.layout(((size_t)sp.maxn / 64 + 1) * 8);
     if (h->ws.p) (void)hipFree(h->ws.release());
-    if (h->ws.alloc(h->o_succ + (size_t)std::max<uint64_t>(h->longest, 1) * 8)) return BVG_E_NOMEM;   // counters + the largest batch: does not fit
-    h->batches.swap(batches); h->maxn = maxn; h->planned = true;
+    if (h->ws.alloc(sp.bytes)) return BVG_E_NOMEM;                               // counters + the largest batch: does not fit
+    sp.bind(h->ws.p);
+    h->sweep = std::move(sp); h->planned = true;
     return 0;
 }
 
@@ -434,31 +396,23 @@ int iterate_impl(bvg_hyperball* h) {
     bvg_graph* g = h->g;
     int rc = ensure_plan(h); if (rc) return rc;
     const bool dbgt = dbg_on();
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    Stopwatch sw;
     double t_dec = 0, t_it = 0;
     unsigned long long* const ctl = (unsigned long long*)h->ctl.p;
     double* const d_total = (double*)(ctl + kCtlWords);
     const int nxt = h->cur ^ 1;
     HIPCHK(hipMemsetAsync(ctl, 0, (kCtlWords + 1) * 8, g->stream));
     HIPCHK(hipMemsetAsync(h->mod[nxt].p, 0, (size_t)h->mod_words * 4, g->stream));
-    char* const w = (char*)h->ws.p;
-    uint64_t* const b_cum = (uint64_t*)(w + h->o_cum); int32_t* const b_deg = (int32_t*)(w + h->o_deg); int64_t* const b_succ = (int64_t*)(w + h->o_succ);
-    double* const b_part = (double*)(w + h->o_part);
+    const bvghost::SweepPlan& sp = h->sweep;
+    double* const b_part = (double*)sp.extra();
     h->inited = false;                                                       // (an error below leaves half an iteration: init first)
-    for (const Batch& b : h->batches) {
+    for (const Batch& b : sp.batches) {
         const int64_t cnt = b.hi - b.lo;
-        const auto t0 = now();
-        if (b.arcs == 0) HIPCHK(hipMemsetAsync(b_cum, 0, ((size_t)cnt + 1) * 8, g->stream));   // (a range the plan left out: empty lists)
-        else {
-            outdegrees_of(g, b.lo, b.hi, b_deg);
-            launch_exclusive_scan(b_deg, b_cum, cnt, (uint64_t*)(w + h->o_tmp), g->stream);
-            rc = run_decode(g, b.lo, b.hi, true, b_cum, b_succ, nullptr, nullptr); if (rc) return rc;
-        }
-        if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); }
-        const auto t1 = now();
+        sw.lap();
+        rc = sp.decode(g, b); if (rc) return rc;
+        if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); t_dec += sw.lap(); }
         IterArgs a;
-        a.cum = b_cum; a.succ = b_succ; a.lo = b.lo; a.cnt = cnt; a.n = h->n;
+        a.cum = sp.cum(); a.succ = sp.succ(); a.lo = b.lo; a.cnt = cnt; a.n = h->n;
         a.cur = (const uint8_t*)h->buf[h->cur].p; a.next = (uint8_t*)h->buf[nxt].p;
         a.cur_mod = (const uint32_t*)h->mod[h->cur].p; a.next_mod = (uint32_t*)h->mod[nxt].p;
         a.sod = (float*)h->sod.p; a.sid = (float*)h->sid.p; a.dist = (double)(h->iteration + 2);
@@ -466,7 +420,7 @@ int iterate_impl(bvg_hyperball* h) {
         HB_DISPATCH(launch_iterate, h, a);
         hipLaunchKernelGGL(hb_reduce_kernel, dim3(1), dim3(256), 0, g->stream, (const double*)b_part, (cnt + 63) / 64, d_total);
         HIPCHK(hipGetLastError());
-        if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); t_dec += ms(t0, t1); t_it += ms(t1, now()); }
+        if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); t_it += sw.lap(); }
     }
     unsigned long long hc[kCtlWords + 1] = {};
     HIPCHK(hipMemcpyAsync(hc, ctl, sizeof hc, hipMemcpyDeviceToHost, g->stream));
@@ -480,7 +434,7 @@ int iterate_impl(bvg_hyperball* h) {
     h->nf.push_back(current);
     h->inited = true;
     if (dbgt) fprintf(stderr, "[bvg] hyperball: iteration %lld: %zu batches, decode %.3f ms, iterate %.3f ms, arcs %llu, passed %llu, modified %llu\n", (long long)h->iteration,
-                      h->batches.size(), t_dec, t_it, (unsigned long long)h->arcs, hc[kCtlPassed], hc[kCtlModified]);
+                      sp.batches.size(), t_dec, t_it, (unsigned long long)sp.arcs, hc[kCtlPassed], hc[kCtlModified]);
     return 0;
 }
 

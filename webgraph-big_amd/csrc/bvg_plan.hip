@@ -333,7 +333,7 @@ int open_common(const bvg_params* p, const uint8_t* h_graph, const void* d_graph
 }
 
 
-// ---- arc-bounded batches: what bvg_components and the visits of bvg_bfs feed their kernels with
+// ---- arc-bounded batches: what bvg_components, the visits of bvg_bfs and the iterations of bvg_hyperball feed their kernels with
 
 // per batch bound j: the prefix sum at the bound and at the node before it (the arcs of a segment without its last list)
 __global__ void gather_bounds_kernel(const uint64_t* cum, const uint64_t* first, uint64_t nb, uint64_t* at, uint64_t* before) {
@@ -364,8 +364,7 @@ int cut_batches(bvg_graph* g, const uint64_t* d_cum, int64_t n, uint64_t arcs, u
     if (first.alloc((nb + 1) * 8) || at.alloc((nb + 1) * 8) || before.alloc((nb + 1) * 8)) return BVG_E_NOMEM;
     uint64_t* const d_first = (uint64_t*)first.p; uint64_t* const d_at = (uint64_t*)at.p; uint64_t* const d_before = (uint64_t*)before.p;
     launch_plan_boundaries(Offsets{nullptr, nullptr, d_cum}, n, per, nb, d_first, g->stream);
-    const uint64_t blocks = (nb + 1 + 255) / 256;
-    hipLaunchKernelGGL(gather_bounds_kernel, dim3((unsigned)(blocks > (1u << 18) ? (1u << 18) : blocks)), dim3(256), 0, g->stream, d_cum, (const uint64_t*)d_first, nb, d_at, d_before);
+    hipLaunchKernelGGL(gather_bounds_kernel, dim3(grid((int64_t)nb + 1, 256)), dim3(256), 0, g->stream, d_cum, (const uint64_t*)d_first, nb, d_at, d_before);
     std::vector<uint64_t> hf(nb + 1), ha(nb + 1), hb(nb + 1);
     HIPCHK(hipMemcpyAsync(hf.data(), first.p, (nb + 1) * 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipMemcpyAsync(ha.data(), at.p, (nb + 1) * 8, hipMemcpyDeviceToHost, g->stream));
@@ -400,6 +399,64 @@ int plan_batches(bvg_graph* g, uint64_t per, std::vector<Batch>& out, uint64_t* 
     HIPCHK(hipStreamSynchronize(g->stream));
     *arcs_out = arcs;
     return cut_batches(g, (const uint64_t*)cum.p, n, arcs, per, out, longest_out);
+}
+
+// ---- the sweep: the whole graph decoded in arc-bounded node ranges, each consumed at once by the caller's kernel
+
+// The residual skip index first, for the whole graph (a no-op when it exists): batches below a quarter of the graph would not build it and
+// would all run on the checking kernels.  A build that fails leaves the batches index-less, nothing worse.
+void index_first(bvg_graph* g) {
+    const int64_t n = g->sh->p.nodes;
+    if (g->tun.no_index != 1 && n >= 4096) (void)bvg_build_index(g, 0, n, nullptr, nullptr);
+}
+
+// The arcs of a batch: half of what is free NOW (the caller's own arrays are allocated, the index is built), less headroom for the decode's own
+// workspaces (256 MiB + 1/16), the node-side arrays of a batch and the planning pass (12 bytes per node); at most `cap`, at least 1.  The test knob
+// `knob_name` (null: none) overrides it when > 0.
+int arc_budget(int64_t n, uint64_t cap, const char* knob_name, uint64_t* per) {
+    if (const char* k = knob_name ? knob(knob_name) : nullptr) { const long long v = atoll(k); if (v > 0) { *per = (uint64_t)v; return 0; } }
+    size_t fr = 0, tot = 0;
+    HIPCHK(hipMemGetInfo(&fr, &tot));
+    const uint64_t head = (256ull << 20) + fr / 16 + (uint64_t)n * 12;
+    *per = std::max<uint64_t>(1, std::min<uint64_t>(cap, fr > head ? (fr - head) / 2 / 8 : 1));
+    return 0;
+}
+
+// plan_batches over the graph.  every_node: every node is in some batch -- the node ranges the plan leaves out (they hold no arcs) become
+// batches of their own with arcs == 0 and at most kMaxBatchNodes nodes, which decode() does not decode (bvg_hyperball: every node has a
+// counter to carry over and to count, its list empty or not).
+int SweepPlan::build(bvg_graph* g, uint64_t per, bool all_nodes) {
+    every_node = all_nodes;
+    const int rc = plan_batches(g, per, batches, &arcs, &longest); if (rc) return rc;
+    if (every_node) {
+        std::vector<Batch> all;
+        int64_t at = 0;
+        auto gap = [&](int64_t to) { for (; at < to; at = std::min(to, at + kMaxBatchNodes)) all.push_back(Batch{at, std::min(to, at + kMaxBatchNodes), 0}); };
+        for (const Batch& b : batches) { gap(b.lo); all.push_back(b); at = b.hi; }
+        gap(g->sh->p.nodes);
+        batches.swap(all);
+    }
+    maxn = 0; for (const Batch& b : batches) maxn = std::max(maxn, b.hi - b.lo);
+    layout(0);
+    return 0;
+}
+
+// the workspace of one batch, 256-byte aligned pieces: maxn + 1 prefix sums, the scan's scratch, maxn outdegrees, `extra_bytes` of the caller's
+// (known once maxn is: bvg_hyperball's per-wavefront partials), then the successors of the largest batch
+void SweepPlan::layout(size_t extra_bytes) {
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    o_tmp = al(((size_t)maxn + 1) * 8); o_deg = o_tmp + al(scan_tmp_elems(maxn) * 8); o_extra = o_deg + al((size_t)maxn * 4); o_succ = o_extra + al(extra_bytes);
+    bytes = o_succ + (size_t)std::max<uint64_t>(longest, 1) * 8;
+}
+
+// the lists of batch b into the bound workspace, on g->stream: list i of node b.lo + i is succ()[cum()[i] .. cum()[i + 1])
+int SweepPlan::decode(bvg_graph* g, const Batch& b) const {
+    const int64_t cnt = b.hi - b.lo;
+    if (every_node && b.arcs == 0) { HIPCHK(hipMemsetAsync(cum(), 0, ((size_t)cnt + 1) * 8, g->stream)); return 0; }   // (a range the plan left out: empty lists)
+    int32_t* const deg = (int32_t*)(base + o_deg);
+    outdegrees_of(g, b.lo, b.hi, deg);
+    launch_exclusive_scan(deg, cum(), cnt, (uint64_t*)(base + o_tmp), g->stream);
+    return run_decode(g, b.lo, b.hi, true, cum(), succ(), nullptr, nullptr);
 }
 
 
