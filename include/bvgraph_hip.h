@@ -221,6 +221,31 @@ int bvg_symmetrize_dev(bvg_graph* g, void* d_soffsets, void* d_ssucc, uint64_t s
 int bvg_components(bvg_graph* g, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components);
 int bvg_components_dev(bvg_graph* g, uint32_t flags, void* d_comp, void* d_sizes, uint64_t sizes_cap, uint64_t* n_components);
 
+/* ---- strongly connected components (algo/StronglyConnectedComponents.java) ----
+ * comp[nodes]: the strongly connected component of every node.  The partition, *n_components, the sizes and the buckets are the
+ * reference's; THE NUMBERING IS NOT: the reference numbers a component when Tarjan's visit emits it, here component c is the one whose
+ * smallest node is the c-th smallest among the components' smallest nodes (the numbering of the weak components above), and with
+ * BVG_SCC_SORT_BY_SIZE (sortBySize) components go by decreasing size, ties by smallest node.  sizes (may be NULL) = computeSizes().
+ * BVG_SCC_BUCKETS (computeBuckets): buckets (required then: one byte per node, 0 / 1) marks the nodes whose component has at least one arc
+ * and no arc leaving it -- a lone node with only a self-loop is a bucket, a node without successors is not.
+ * The computation sweeps the compressed graph over forward arcs only (trimming, one forward-backward step from the live node of largest
+ * outdegree, then colouring rounds: DESIGN.md 7e): no transpose, and the graph never has to fit in HBM as a CSR.  Device memory: two
+ * elements (4 bytes each; 8 on the 64-bit kernels) and one byte per node, one arc-bounded batch of the decode (as the weak components),
+ * 12 bytes per node while numbering; BVG_E_NOMEM leaves g usable.  The cost is one sweep per step of the longest propagation: a chain of k
+ * nodes costs about k / 2 sweeps.  counters (may be NULL): out[BVG_SCC_COUNTERS] = sweeps, batch decodes, trim passes, nodes retired by
+ * trimming, size of the forward-backward component, colouring rounds, components found by colouring, 1 if a single resident batch was used.
+ * g, n_components NULL, unknown flag bits, BVG_SCC_BUCKETS without buckets, node_base != 0: BVG_E_ARG, checked before any device call.  sizes_cap
+ * below the count: BVG_E_CAPACITY, *n_components and comp written all the same.  An empty graph has 0 components.  Malformed streams report
+ * the decode's status (a successor outside [0, nodes): BVG_E_EOF, never used as an index).  _dev: comp / sizes (int64) and buckets (bytes)
+ * in device memory. */
+#define BVG_SCC_SORT_BY_SIZE 1u
+#define BVG_SCC_BUCKETS      2u
+#define BVG_SCC_COUNTERS     8
+int bvg_scc(bvg_graph* g, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap,
+            uint64_t* n_components, uint8_t* buckets, uint64_t* counters);
+int bvg_scc_dev(bvg_graph* g, uint32_t flags, void* d_comp, void* d_sizes, uint64_t sizes_cap,
+                uint64_t* n_components, void* d_buckets, uint64_t* counters);
+
 /* ---- breadth-first visits (algo/ParallelBreadthFirstVisit.java) ----
  * A visit object keeps on the device what the reference's class keeps (ParallelBreadthFirstVisit.java:79-148): marker[nodes] (-1 = not
  * enqueued yet; otherwise the round in which the node was reached, or its parent with BVG_BFS_PARENT), the round counter (-1 before the

@@ -1,0 +1,293 @@
+"""GPU: strongly connected components on the device (bvg_scc; algo/StronglyConnectedComponents.java).
+
+Every expected answer comes from the CPU (tests/scc_cases.py: scipy's connected_components(connection="strong") when it is importable, an
+iterative Tarjan otherwise), canonicalised to the library's numbering; count, component, sizes and buckets are compared exactly.  A
+synchronous numpy model of trimming plus colouring alone (no forward-backward step) needs 358 sweeps on cnr-2000 and 57 on
+sweep_cases.empty_runs_graph(): the device needs fewer or more depending on what propagates inside a launch, so no sweep count is
+asserted, only what the counters must show."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import scc_cases
+import sweep_cases
+from scc_cases import arcs_of, cpu_scc, csr_of, sorted_by_size
+from test_gpu_components import ROUTES
+
+GOLDEN_CNR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "cnr-2000")
+
+pytestmark = pytest.mark.gpu
+
+
+def check(g, n, src, dst, sort=True, expect=None, plain=True):
+    k, comp, sizes, buckets = expect if expect is not None else cpu_scc(n, src, dst)
+    r = g.strongly_connected_components(sizes=True, buckets=True)
+    assert r.count == k
+    assert np.array_equal(r.component, comp)
+    assert np.array_equal(r.sizes, sizes)
+    assert r.buckets.dtype == bool and np.array_equal(r.buckets, buckets)
+    if plain:                                                                  # (off where every sweep decodes hundreds of tiny batches)
+        p = g.strongly_connected_components()
+        assert p.sizes is None and p.buckets is None and p.count == k and np.array_equal(p.component, comp)
+    if sort:
+        rs = g.strongly_connected_components(sizes=True, sort_by_size=True, buckets=True)
+        c2, s2 = sorted_by_size(comp, sizes)
+        assert rs.count == k and np.array_equal(rs.component, c2) and np.array_equal(rs.sizes, s2) and np.array_equal(rs.buckets, buckets)
+    return r
+
+
+def graph_of(W, tools, off, adj, params=None, threads=2):
+    st = tools.store((off, adj), params, threads=threads) if params is not None else tools.store((off, adj), threads=threads)
+    return W.BVGraph.from_memory(st.params, st.graph, st.offsets)
+
+
+@pytest.fixture(scope="module")
+def cnr_expected(cnr_csr):
+    deg, succ = cnr_csr
+    src = np.repeat(np.arange(len(deg), dtype=np.int64), deg)
+    return src, succ, cpu_scc(len(deg), src, succ)
+
+
+# 1. the golden graph
+def test_cnr2000_known_answers(W, cnr_expected):
+    src, dst, expect = cnr_expected
+    k, comp, sizes, buckets = expect
+    assert scc_cases.summary(k, comp, sizes, buckets, src, dst) == scc_cases.CNR   # (the issue's known answers, scipy)
+    g = W.BVGraph.load(GOLDEN_CNR)
+    n = g.num_nodes()
+    for h in (g, g.copy()):
+        r = check(h, n, src, dst, expect=expect)
+        c = r.counters
+        print("cnr-2000 counters:", c)
+        assert c["trimmed_nodes"] > 0 and c["trim_passes"] > 0                   # trimming retired nodes
+        assert c["fwbw_component"] > 1                                           # the FW-BW step found a component of more than one node
+        assert c["colouring_rounds"] >= 1 and c["colouring_components"] >= 1     # and left some for the colouring
+        assert c["single_resident_batch"] == 1 and c["batch_decodes"] == 1       # on one batch, decoded once
+        assert c["trimmed_nodes"] + c["fwbw_component"] <= n and c["sweeps"] >= c["trim_passes"] + c["colouring_rounds"]
+
+
+# 2. hand graphs
+def _cycle(lo, hi):
+    return [(x, x + 1) for x in range(lo, hi - 1)] + [(hi - 1, lo)]
+
+
+HAND = {
+    "one_node": (1, [], 1, [False]),
+    "one_self_loop": (1, [(0, 0)], 1, [True]),
+    "two_cycle": (2, [(0, 1), (1, 0)], 1, [True, True]),
+    "two_cycle_and_sink": (3, [(0, 1), (1, 0), (1, 2)], 2, [False, False, False]),
+    "path_300": (300, [(x, x + 1) for x in range(299)], 300, [False] * 300),
+    "cycle_300": (300, _cycle(0, 300), 1, [True] * 300),
+    "two_cycles_joined": (300, _cycle(0, 150) + _cycle(150, 300) + [(7, 200)], 2, [False] * 150 + [True] * 150),
+    # the largest id (9) and the largest outdegree (node 2, the pivot) are different nodes of the cycle; 10 and 11 hang off it
+    "cycle_pivot_not_largest": (12, _cycle(0, 10) + [(2, 5), (2, 7), (2, 10), (11, 3)], 3, [False] * 12),
+}
+
+
+@pytest.mark.parametrize("name", sorted(HAND))
+def test_hand_graphs(W, tools, name):
+    n, arcs, k, buckets = HAND[name]
+    off, adj = csr_of(n, arcs)
+    g = graph_of(W, tools, off, adj)
+    src, dst = arcs_of(off, adj)
+    expect = cpu_scc(n, src, dst)
+    assert expect[0] == k and expect[3].tolist() == buckets                     # (the oracle agrees with the answer written down here)
+    r = check(g, n, src, dst, expect=expect)
+    if name == "cycle_pivot_not_largest":
+        assert r.counters["fwbw_component"] == 10
+    if name == "path_300":
+        assert r.counters["trimmed_nodes"] == 300 and r.counters["trim_passes"] >= 150
+
+
+def test_empty_graph(W, tools):
+    st = tools.store([])
+    g = W.BVGraph.from_memory(st.params, st.graph, st.offsets)
+    r = g.strongly_connected_components(sizes=True, buckets=True, sort_by_size=True)
+    assert r.count == 0 and len(r.component) == 0 and len(r.sizes) == 0 and len(r.buckets) == 0
+
+
+# 3. synthetic graphs under every decode route
+@pytest.mark.parametrize("route", sorted(ROUTES))
+@pytest.mark.parametrize("shape,seed", [("web", 1), ("eu", 3)])
+def test_synthetic_graphs_every_route(W, tools, route, shape, seed):
+    n = 6000 if shape == "eu" else 20000
+    synth = tools.web_like(p_empty=0.5, mean_deg=4.0, local_gap=40.0) if shape == "web" else tools.eu_like(p_empty=0.3, mean_deg=30.0)
+    off, adj = tools.synth_adjacency(n, seed=seed, synth=synth)
+    if shape == "eu":                                                          # (one giant component otherwise: cut it into blocks of 700 nodes)
+        off, adj, _ = scc_cases.cut(*arcs_of(off, adj), n, 700)
+    g = graph_of(W, tools, off, adj, threads=4)
+    if ROUTES[route]:
+        g.set_tuning(**ROUTES[route])
+    src, dst = arcs_of(off, adj)
+    expect = cpu_scc(n, src, dst)
+    assert (expect[2] > 1).sum() > 1                                           # more than one SCC of more than one node
+    check(g, n, src, dst, sort=route == "default", expect=expect)
+
+
+def test_window_above_64_takes_the_slow_kernel(W, tools):
+    n = 5000
+    off, adj = tools.synth_adjacency(n, seed=9, synth=tools.web_like(p_empty=0.5, mean_deg=4.0))
+    g = graph_of(W, tools, off, adj, W.default_params(window_size=70, max_ref_count=-1), threads=4)
+    check(g, n, *arcs_of(off, adj))
+
+
+# 4. batch boundaries: SCCs span batches, lists longer than the budget
+def test_batch_boundaries_do_not_change_the_result(W, tools, monkeypatch):
+    n = 3000
+    off, adj = tools.synth_adjacency(n, seed=5, synth=tools.web_like(p_empty=0.4, mean_deg=6.0, max_deg=400, local_gap=200.0))
+    assert np.diff(off.astype(np.int64)).max() > 97                            # some lists exceed the small budget
+    src, dst = arcs_of(off, adj)
+    expect = cpu_scc(n, src, dst)
+    assert expect[2].max() > 97                                                # an SCC that spans several batches of 97 arcs
+    got = {}
+    for budget in ("97", None):
+        if budget is None:
+            monkeypatch.delenv("BVG_SCC_BATCH_ARCS", raising=False)
+        else:
+            monkeypatch.setenv("BVG_SCC_BATCH_ARCS", budget)
+        g = graph_of(W, tools, off, adj)
+        got[budget] = check(g, n, src, dst, sort=False, expect=expect, plain=budget is None)
+    a, b = got["97"], got[None]
+    assert np.array_equal(a.component, b.component) and np.array_equal(a.sizes, b.sizes) and np.array_equal(a.buckets, b.buckets)
+    assert a.counters["single_resident_batch"] == 0 and a.counters["batch_decodes"] > a.counters["sweeps"]
+    assert b.counters["single_resident_batch"] == 1 and b.counters["batch_decodes"] == 1
+
+
+# 5. long runs of nodes without successors: node ranges the batch plan leaves out.  (Not budget "1": every sweep costs one decode per batch.)
+@pytest.mark.parametrize("budget", ["7", "97"])
+def test_empty_runs_under_tiny_budgets(W, tools, monkeypatch, budget):
+    monkeypatch.setenv("BVG_SCC_BATCH_ARCS", budget)
+    off, adj = sweep_cases.empty_runs_graph()
+    assert np.diff(off.astype(np.int64)).max() > int(budget)                   # the longest list exceeds the budget
+    n = len(off) - 1
+    src, dst = arcs_of(off, adj)
+    expect = cpu_scc(n, src, dst)
+    assert expect[0] == 986 and expect[2].max() == 10
+    g = graph_of(W, tools, off, adj)
+    r = check(g, n, src, dst, sort=False, expect=expect, plain=False)
+    assert r.counters["batch_decodes"] > r.counters["sweeps"]
+
+
+# 6. neither the pivot nor the scheduling reaches the result
+def test_result_does_not_depend_on_the_pivot(W, tools, monkeypatch):
+    n = 20000
+    off, adj = tools.synth_adjacency(n, seed=2, synth=tools.web_like(p_empty=0.5, mean_deg=4.0, local_gap=40.0))
+    src, dst = arcs_of(off, adj)
+    expect = cpu_scc(n, src, dst)
+    k, comp, sizes, _ = expect
+    giant = int(np.flatnonzero(comp == int(np.argmax(sizes)))[3])              # some node of the giant SCC
+    trimmed = int(np.flatnonzero(np.diff(off.astype(np.int64)) == 0)[0])       # a node without successors: the first trim pass retires it
+    g = graph_of(W, tools, off, adj, threads=4)
+    seen = {}
+    for pivot in (None, "none", str(giant), str(trimmed)):
+        if pivot is None:
+            monkeypatch.delenv("BVG_SCC_PIVOT", raising=False)
+        else:
+            monkeypatch.setenv("BVG_SCC_PIVOT", pivot)
+        seen[pivot] = check(g, n, src, dst, sort=False, expect=expect).counters
+    assert seen["none"]["fwbw_component"] == 0 and seen[str(trimmed)]["fwbw_component"] == 0
+    assert seen[str(giant)]["fwbw_component"] == int(sizes.max())
+    assert seen[None]["fwbw_component"] > 1
+
+
+def test_two_runs_are_identical(W, tools):
+    n = 200000
+    off, adj = tools.synth_adjacency(n, seed=13, synth=tools.web_like(p_empty=0.3, mean_deg=3.0, local_gap=50.0, p_far=0.2))
+    g = graph_of(W, tools, off, adj, threads=4)
+    a = g.strongly_connected_components(sizes=True, sort_by_size=True, buckets=True)
+    b = g.copy().strongly_connected_components(sizes=True, sort_by_size=True, buckets=True)
+    assert a.count == b.count and np.array_equal(a.component, b.component) and np.array_equal(a.sizes, b.sizes) and np.array_equal(a.buckets, b.buckets)
+    k, comp, sizes, buckets = cpu_scc(n, *arcs_of(off, adj))
+    c2, s2 = sorted_by_size(comp, sizes)
+    assert a.count == k and np.array_equal(a.component, c2) and np.array_equal(a.sizes, s2) and np.array_equal(a.buckets, buckets)
+
+
+# 7. the contract
+def test_capacity_and_flags(W, tools):
+    n = 4000
+    off, adj = tools.synth_adjacency(n, seed=21, synth=tools.web_like(p_empty=0.5, mean_deg=3.0))
+    g = graph_of(W, tools, off, adj)
+    k, comp, sizes, _ = cpu_scc(n, *arcs_of(off, adj))
+    L = W.bvgraph._scc_fns()
+    comp_buf = np.full(n, -7, dtype=np.int64); sz = np.zeros(4, dtype=np.int64); cnt = C.c_uint64()
+    assert L.bvg_scc(g._h, 0, comp_buf.ctypes.data, sz.ctypes.data, 4, C.byref(cnt), None, None) == W.E_CAPACITY
+    assert cnt.value == k and np.array_equal(comp_buf, comp)                   # the count and comp written all the same
+    assert L.bvg_scc(g._h, 4, comp_buf.ctypes.data, None, 0, C.byref(cnt), None, None) == W.E_ARG        # unknown flag bits
+    assert L.bvg_scc(g._h, W.SCC_BUCKETS, comp_buf.ctypes.data, None, 0, C.byref(cnt), None, None) == W.E_ARG   # buckets asked for, no array
+    assert L.bvg_scc(g._h, 0, comp_buf.ctypes.data, None, 0, None, None, None) == W.E_ARG                # no count
+    assert L.bvg_scc(g._h, 0, None, None, 0, C.byref(cnt), None, None) == W.E_ARG                        # no comp
+    assert L.bvg_scc(g._h, 0, comp_buf.ctypes.data, sz.ctypes.data, 4, C.byref(cnt), None, None) == W.E_CAPACITY and cnt.value == k   # g is usable after every refusal
+
+
+def test_shard_handle_is_refused(W, tools):
+    off, adj = tools.synth_adjacency(1000, seed=1)
+    g = graph_of(W, tools, off, adj)
+    g.set_node_base(1000)
+    with pytest.raises(W.IllegalArgumentException):
+        g.strongly_connected_components()
+
+
+def test_successor_outside_the_graph_is_eof(W):
+    from bvrecords import Record, assemble
+    recs = [Record(d=2, residuals=[1, 2]), Record(d=1, residuals=[0]), Record(d=1, residuals=[9])]   # node 2 -> 9 in a 3-node graph
+    gbytes, offs, _ = assemble(recs)
+    p = W.default_params().clone(nodes=3, arcs=4)
+    g = W.BVGraph.from_memory(p, np.frombuffer(gbytes, dtype=np.uint8), offs)
+    with pytest.raises(W.EOFException):
+        g.strongly_connected_components(buckets=True)
+
+
+def test_tiled_graph(W, tools):
+    n0, K = 4000, 7
+    off, adj = tools.synth_adjacency(n0, seed=21, synth=tools.web_like(p_empty=0.5, mean_deg=3.0))
+    base = graph_of(W, tools, off, adj)
+    c0, comp0, sizes0, buckets0 = cpu_scc(n0, *arcs_of(off, adj))
+    r = base.tile(K).strongly_connected_components(sizes=True, buckets=True)
+    assert r.count == K * c0
+    expect = (np.arange(K, dtype=np.int64)[:, None] * c0 + comp0[None, :]).ravel()     # copy j: the base's labels plus j * c0
+    assert np.array_equal(r.component, expect) and np.array_equal(r.sizes, np.tile(sizes0, K)) and np.array_equal(r.buckets, np.tile(buckets0, K))
+
+
+# 8. device buffers (a child process that imports torch before the product library: tests/test_gpu_device_buffers.py)
+def _body_device_buffers(W, tools, torch):
+    n = 30000
+    off, adj = tools.synth_adjacency(n, seed=17, synth=tools.web_like(p_empty=0.5, mean_deg=3.0))
+    st = tools.store((off, adj), threads=4)
+    g = W.BVGraph.from_memory(st.params, st.graph, st.offsets)
+    k, comp, sizes, buckets = cpu_scc(n, *arcs_of(off, adj))
+    assert buckets.any()
+    dc = torch.empty(n, dtype=torch.int64, device="cuda"); ds = torch.empty(k, dtype=torch.int64, device="cuda"); db = torch.full((n,), 7, dtype=torch.uint8, device="cuda")
+    count, counters = g.strongly_connected_components_dev(dc, ds, db)
+    assert count == k and counters["sweeps"] > 0
+    assert np.array_equal(dc.cpu().numpy(), comp) and np.array_equal(ds.cpu().numpy(), sizes) and np.array_equal(db.cpu().numpy(), buckets.astype(np.uint8))
+    dc.fill_(-1)
+    try:
+        g.strongly_connected_components_dev(dc, torch.empty(k - 1, dtype=torch.int64, device="cuda"))
+        raise AssertionError("no IllegalArgumentException for a short sizes buffer")
+    except W.IllegalArgumentException:
+        pass
+    assert np.array_equal(dc.cpu().numpy(), comp)                             # comp written all the same
+    c2, s2 = sorted_by_size(comp, sizes)
+    assert g.strongly_connected_components_dev(dc, ds, sort_by_size=True)[0] == k
+    assert np.array_equal(dc.cpu().numpy(), c2) and np.array_equal(ds.cpu().numpy(), s2)
+
+
+def test_device_buffers_match_host():
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "device_buffers"], capture_output=True, text=True, timeout=560)
+    assert r.returncode == 0 and "CHILD OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+if __name__ == "__main__":
+    import torch                                                              # (before the product library)
+    torch.cuda.init()
+    _HERE = os.path.dirname(os.path.abspath(__file__))
+    sys.path[:0] = [os.path.dirname(_HERE), _HERE]
+    import tooling
+    import webgraph_big_amd
+    tooling.lib()
+    globals()["_body_" + sys.argv[1]](webgraph_big_amd, tooling, torch)
+    print("CHILD OK")

@@ -14,4 +14,5 @@ from .bvgraph import (BVGraph, NodeIterator, LazyLongIterator, BVGraphError, Ill
                       scan_multi, mosaic, BALANCE_NODES, BALANCE_BITS, BALANCE_ARCS, store,
                       CC_SORT_BY_SIZE, ComponentsResult, store_components, load_components, components_main,
                       BFS_PARENT, BFS_COUNTERS, BreadthFirstVisit,
+                      SCC_SORT_BY_SIZE, SCC_BUCKETS, SCC_COUNTERS, SCCResult, store_scc, load_scc, scc_main,
                       HB_SUM_OF_DISTANCES, HB_HARMONIC, HyperBall, hyperball_main, store_floats, load_floats)

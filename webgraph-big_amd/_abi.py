@@ -66,6 +66,18 @@ def hyperball_signatures():
             "bvg_hyperball_centrality": [vp, C.c_int, vp], "bvg_hyperball_centrality_dev": [vp, C.c_int, vp],
             "bvg_hyperball_relative_standard_deviation": [C.c_int]}
 
+
+# bvg_scc flags / the number of words it writes to `counters` (BVG_SCC_SORT_BY_SIZE, BVG_SCC_BUCKETS, BVG_SCC_COUNTERS)
+SCC_SORT_BY_SIZE_FLAG, SCC_BUCKETS_FLAG, SCC_COUNTER_WORDS = 1, 2, 8
+
+
+def scc_signatures():
+    """argtypes of bvg_scc / bvg_scc_dev (strongly connected components), by name."""
+    vp, u64 = C.c_void_p, C.c_uint64
+    args = [vp, C.c_uint32, vp, vp, u64, C.POINTER(u64), vp, vp]
+    return {"bvg_scc": list(args), "bvg_scc_dev": list(args)}
+
+
 OK, E_ARG, E_STATE, E_UNSUPPORTED, E_IO, E_EOF, E_NOMEM, E_HIP, E_CAPACITY = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 

@@ -182,6 +182,19 @@ def _bfs_fns():
     return L
 
 
+def _scc_fns():
+    """bvg_scc / bvg_scc_dev, bound on first use (as _components_fns)."""
+    L = lib()
+    if getattr(L, "_scc_bound", False):
+        return L
+    for name, args in _abi.scc_signatures().items():
+        if not hasattr(L, name):
+            raise UnsupportedOperationException(_abi.E_UNSUPPORTED, name + " is not in this build of the library")
+        getattr(L, name).argtypes = args
+    L._scc_bound = True
+    return L
+
+
 def _hyperball_fns():
     """The bvg_hyperball_* entry points, bound on first use (as _bfs_fns)."""
     L = lib()
@@ -813,6 +826,53 @@ class BVGraph:
         _check(st, "connected_components_dev")
         return int(cnt.value)
 
+    def strongly_connected_components(self, sizes=False, sort_by_size=False, buckets=False):
+        """StronglyConnectedComponents.compute (algo/StronglyConnectedComponents.java) on the device (bvg_scc): sweeps of the
+        compressed graph over forward arcs only -- trimming, one forward-backward step, colouring rounds.  The partition, the count,
+        the sizes and the buckets are the reference's; the numbering is not Tarjan's emission order: component c is the one whose
+        smallest node is the c-th smallest among the components' smallest nodes, and sort_by_size=True (sortBySize) renumbers by
+        decreasing size, ties by smallest node.  sizes=True also returns computeSizes(); buckets=True the computeBuckets() set as one
+        bool per node (its component has an arc and none that leaves it).  Returns an SCCResult."""
+        L = _scc_fns()
+        n = self.num_nodes()
+        comp = np.empty(max(n, 1), dtype=np.int64)
+        cnt = C.c_uint64(0)
+        flags = (SCC_SORT_BY_SIZE if sort_by_size else 0) | (SCC_BUCKETS if buckets else 0)
+        cap = max(n, 1) if sizes else 0
+        sz = np.empty(cap, dtype=np.int64) if sizes else None
+        bk = np.zeros(max(n, 1), dtype=np.uint8) if buckets else None
+        ctr = np.zeros(_abi.SCC_COUNTER_WORDS, dtype=np.uint64)
+        _check(L.bvg_scc(self._h, flags, comp.ctypes.data, None if sz is None else sz.ctypes.data, cap, C.byref(cnt),
+                         None if bk is None else bk.ctypes.data, ctr.ctypes.data), "strongly_connected_components")
+        k = int(cnt.value)
+        return SCCResult(k, comp[:n], None if sz is None else sz[:k], None if bk is None else bk[:n].astype(bool),
+                         dict(zip(SCC_COUNTERS, (int(v) for v in ctr))))
+
+    stronglyConnectedComponents = strongly_connected_components
+
+    def strongly_connected_components_dev(self, comp_tensor, sizes_tensor=None, buckets_tensor=None, sort_by_size=False):
+        """bvg_scc_dev: labels into comp_tensor (int64, numNodes() elements, on the graph's device), when given sizes into
+        sizes_tensor (int64; BVG_E_CAPACITY -> IllegalArgumentException if it holds fewer than the count) and the buckets into
+        buckets_tensor (uint8, numNodes() elements, 0 / 1).  Returns (count, counters)."""
+        import torch
+        L = _scc_fns()
+        n = self.num_nodes()
+        for t, what, dt in ((comp_tensor, "comp", torch.int64), (sizes_tensor, "sizes", torch.int64), (buckets_tensor, "buckets", torch.uint8)):
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
+                raise IllegalArgumentException(_abi.E_ARG, "%s must be a contiguous %s CUDA tensor" % (what, dt))
+        for t, what in ((comp_tensor, "comp"), (buckets_tensor, "buckets")):
+            if t is not None and t.numel() < n:
+                raise IllegalArgumentException(_abi.E_ARG, "%s holds %d elements, the graph %d nodes" % (what, t.numel(), n))
+        cnt = C.c_uint64(0)
+        ctr = np.zeros(_abi.SCC_COUNTER_WORDS, dtype=np.uint64)
+        flags = (SCC_SORT_BY_SIZE if sort_by_size else 0) | (SCC_BUCKETS if buckets_tensor is not None else 0)
+        st = L.bvg_scc_dev(self._h, flags, comp_tensor.data_ptr() if n else None, None if sizes_tensor is None else sizes_tensor.data_ptr(),
+                           0 if sizes_tensor is None else sizes_tensor.numel(), C.byref(cnt), None if buckets_tensor is None else buckets_tensor.data_ptr(), ctr.ctypes.data)
+        if st == _abi.E_CAPACITY:
+            raise IllegalArgumentException(st, "strongly_connected_components_dev: %d components, sizes holds %d" % (int(cnt.value), sizes_tensor.numel()))
+        _check(st, "strongly_connected_components_dev")
+        return int(cnt.value), dict(zip(SCC_COUNTERS, (int(v) for v in ctr)))
+
     def breadth_first_visit(self, parent=False):
         """ParallelBreadthFirstVisit (algo/ParallelBreadthFirstVisit.java) with its state on the device: see BreadthFirstVisit."""
         return BreadthFirstVisit(self, parent)
@@ -854,6 +914,8 @@ class BVGraph:
 BALANCE_NODES, BALANCE_BITS, BALANCE_ARCS = 0, 1, 2
 CC_SORT_BY_SIZE = 1
 BFS_PARENT = 1
+SCC_SORT_BY_SIZE, SCC_BUCKETS = 1, 2
+SCC_COUNTERS = ("sweeps", "batch_decodes", "trim_passes", "trimmed_nodes", "fwbw_component", "colouring_rounds", "colouring_components", "single_resident_batch")
 BFS_COUNTERS = ("frontier_levels", "sweep_levels", "deep_requests", "frontier_batches", "sweep_batches", "sorted_levels", "compacted_levels", "first_level_route")
 
 
@@ -1227,6 +1289,78 @@ def components_main(argv=None):
     finally:
         g.close()
     store_components(r, out)
+    print("%d components" % r.count)
+    return r
+
+
+class SCCResult:
+    """What StronglyConnectedComponents holds after compute(): numberOfComponents (count), component[] (int64 per node; numbered by
+    smallest node, not in Tarjan's emission order), computeSizes() (sizes, or None), the buckets as one bool per node (or None:
+    computeBuckets was false) and the counters of bvg_scc by name (SCC_COUNTERS)."""
+
+    def __init__(self, count, component, sizes=None, buckets=None, counters=None):
+        self.count, self.component, self.sizes, self.buckets, self.counters = int(count), component, sizes, buckets, counters or {}
+
+    numberOfComponents = property(lambda self: self.count)
+
+    def __repr__(self):
+        return "SCCResult(count=%d, nodes=%d, sizes=%s, buckets=%s)" % (self.count, len(self.component), "yes" if self.sizes is not None else "no",
+                                                                        "yes" if self.buckets is not None else "no")
+
+
+def store_scc(result, results_basename):
+    """StronglyConnectedComponents.main's output files: results_basename.scc = the component of every node and, when the result has
+    sizes, results_basename.sccsizes = the size of every component, each as BinIO.storeLongs writes them (big-endian int64, no header).
+    When the result has buckets, results_basename.bucketbits: ceil(n / 8) bytes, bit x & 7 of byte x >> 3 (the least significant bit
+    first) set when node x is in a bucket.  The reference's .buckets is a Java-serialised LongArrayBitVector and is NOT written.
+    Returns the paths written."""
+    paths = [results_basename + ".scc"]
+    np.asarray(result.component, dtype=">i8").tofile(paths[0])
+    if result.sizes is not None:
+        paths.append(results_basename + ".sccsizes")
+        np.asarray(result.sizes, dtype=">i8").tofile(paths[-1])
+    if result.buckets is not None:
+        paths.append(results_basename + ".bucketbits")
+        np.packbits(np.asarray(result.buckets, dtype=bool), bitorder="little").tofile(paths[-1])
+    return paths
+
+
+def load_scc(results_basename, nodes=None):
+    """Reads back what store_scc wrote: (component, sizes or None, buckets or None) -- int64 arrays and one bool per node (nodes: the
+    length of the bucket array; default: that of the component array)."""
+    comp = np.fromfile(results_basename + ".scc", dtype=">i8").astype(np.int64)
+    sp, bp = results_basename + ".sccsizes", results_basename + ".bucketbits"
+    sizes = np.fromfile(sp, dtype=">i8").astype(np.int64) if os.path.exists(sp) else None
+    buckets = None
+    if os.path.exists(bp):
+        buckets = np.unpackbits(np.fromfile(bp, dtype=np.uint8), bitorder="little")[:len(comp) if nodes is None else nodes].astype(bool)
+    return comp, sizes, buckets
+
+
+def scc_arg_parser():
+    """The command line of StronglyConnectedComponents.main: basename [resultsBasename], -s/--sizes, -r/--renumber, -b/--buckets."""
+    import argparse
+    ap = argparse.ArgumentParser(prog="scc", description="Strongly connected components of a BVGraph, computed on the device.")
+    ap.add_argument("-s", "--sizes", action="store_true", help="also store the component sizes (resultsBasename.sccsizes)")
+    ap.add_argument("-r", "--renumber", action="store_true", help="renumber components by decreasing size (ties: smallest node first)")
+    ap.add_argument("-b", "--buckets", action="store_true", help="also store the buckets as a bit array (resultsBasename.bucketbits: n bits, LSB first)")
+    ap.add_argument("--device", type=int, default=0, help="the GPU to run on")
+    ap.add_argument("basename", help="the basename of the graph")
+    ap.add_argument("results_basename", nargs="?", default=None, help="the basename of the result files (default: the graph's basename)")
+    return ap
+
+
+def scc_main(argv=None):
+    """StronglyConnectedComponents.main: loads basename, computes the components, writes resultsBasename.scc (.sccsizes with -s,
+    .bucketbits with -b: see store_scc)."""
+    args = scc_arg_parser().parse_args(argv)
+    out = args.results_basename or args.basename
+    g = BVGraph.load(args.basename, device=args.device)
+    try:
+        r = g.strongly_connected_components(sizes=args.sizes, sort_by_size=args.renumber, buckets=args.buckets)
+    finally:
+        g.close()
+    store_scc(r, out)
     print("%d components" % r.count)
     return r
 

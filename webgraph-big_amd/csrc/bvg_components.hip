@@ -168,45 +168,11 @@ namespace {
 
 using bvghost::DevBuf;
 
-template <typename T> int components_t(bvg_graph* g, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components, bool dev) {
-    Shared* sh = g->sh; const int64_t n = sh->p.nodes;
-    const bool dbgt = dbg_on();
-    Stopwatch sw;
-    index_first(g);
-    DevBuf parent;
-    if (parent.alloc((size_t)n * sizeof(T))) return BVG_E_NOMEM;
-    T* const d_parent = (T*)parent.p;
-    hipLaunchKernelGGL((cc_init_kernel<T>), dim3(grid(n, 256)), dim3(256), 0, g->stream, d_parent, n);
-    uint64_t per = 0;                                                       // (of what is free once the parent array is there)
-    int rc = arc_budget(n, kMaxBatchArcs, "BVG_CC_BATCH_ARCS", &per); if (rc) return rc;
-    SweepPlan sp;
-    rc = sp.build(g, per); if (rc) return rc;
-    const double t_plan = sw.lap();
-    double t_dec = 0, t_hook = 0;
-    DevBuf d_bad;
-    if (d_bad.alloc(256)) return BVG_E_NOMEM;
-    HIPCHK(hipMemsetAsync(d_bad.p, 0, sizeof(unsigned), g->stream));
-    if (!sp.batches.empty()) {
-        DevBuf ws;                                                          // (this scope: gone before the numbering pass, which needs the memory)
-        if (ws.alloc(sp.bytes)) return BVG_E_NOMEM;                         // parent array + the largest batch: does not fit
-        sp.bind(ws.p);
-        for (const Batch& b : sp.batches) {
-            const int64_t cnt = b.hi - b.lo;
-            sw.lap();
-            rc = sp.decode(g, b); if (rc) return rc;
-            if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); t_dec += sw.lap(); }
-            hipLaunchKernelGGL((cc_hook_kernel<T>), dim3(grid(cnt, 256)), dim3(256), 0, g->stream, (const uint64_t*)sp.cum(), b.lo, cnt, (const int64_t*)sp.succ(), n, d_parent,
-                               (unsigned*)d_bad.p);
-            HIPCHK(hipGetLastError());
-            if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); t_hook += sw.lap(); }
-        }
-    }
-    unsigned bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, d_bad.p, sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
-    if (bad) return BVG_E_EOF;                                              // a successor outside [0, n): malformed stream
-    sw.lap();
-    // compress + number (the batch buffer is gone by now)
+// compress + number + sizes + sort over a parent array whose trees are complete (the batch buffer is gone by now): what bvg_components
+// and bvg_scc (there parent[x] is the smallest node of x's component already) share through number_components (bvg_host.h).
+// 0 or BVG_E_CAPACITY (sizes_cap below the count; comp and the count written all the same); *count_out: the count
+template <typename T> int number_t(bvg_graph* g, T* d_parent, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components, bool dev, uint64_t* count_out) {
+    const int64_t n = g->sh->p.nodes;
     DevBuf flag, rank, tmp, dcomp;
     if (flag.alloc((size_t)n * 4) || rank.alloc(((size_t)n + 1) * 8) || tmp.alloc(scan_tmp_elems(n) * 8)) return BVG_E_NOMEM;
     int64_t* d_comp = comp;
@@ -251,9 +217,54 @@ template <typename T> int components_t(bvg_graph* g, uint32_t flags, int64_t* co
     }
     if (!dev) HIPCHK(hipMemcpy(comp, d_comp, (size_t)n * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipGetLastError());
+    *count_out = count;
+    return cap_ok ? 0 : BVG_E_CAPACITY;
+}
+
+template <typename T> int components_t(bvg_graph* g, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components, bool dev) {
+    Shared* sh = g->sh; const int64_t n = sh->p.nodes;
+    const bool dbgt = dbg_on();
+    Stopwatch sw;
+    index_first(g);
+    DevBuf parent;
+    if (parent.alloc((size_t)n * sizeof(T))) return BVG_E_NOMEM;
+    T* const d_parent = (T*)parent.p;
+    hipLaunchKernelGGL((cc_init_kernel<T>), dim3(grid(n, 256)), dim3(256), 0, g->stream, d_parent, n);
+    uint64_t per = 0;                                                       // (of what is free once the parent array is there)
+    int rc = arc_budget(n, kMaxBatchArcs, "BVG_CC_BATCH_ARCS", &per); if (rc) return rc;
+    SweepPlan sp;
+    rc = sp.build(g, per); if (rc) return rc;
+    const double t_plan = sw.lap();
+    double t_dec = 0, t_hook = 0;
+    DevBuf d_bad;
+    if (d_bad.alloc(256)) return BVG_E_NOMEM;
+    HIPCHK(hipMemsetAsync(d_bad.p, 0, sizeof(unsigned), g->stream));
+    if (!sp.batches.empty()) {
+        DevBuf ws;                                                          // (this scope: gone before the numbering pass, which needs the memory)
+        if (ws.alloc(sp.bytes)) return BVG_E_NOMEM;                         // parent array + the largest batch: does not fit
+        sp.bind(ws.p);
+        for (const Batch& b : sp.batches) {
+            const int64_t cnt = b.hi - b.lo;
+            sw.lap();
+            rc = sp.decode(g, b); if (rc) return rc;
+            if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); t_dec += sw.lap(); }
+            hipLaunchKernelGGL((cc_hook_kernel<T>), dim3(grid(cnt, 256)), dim3(256), 0, g->stream, (const uint64_t*)sp.cum(), b.lo, cnt, (const int64_t*)sp.succ(), n, d_parent,
+                               (unsigned*)d_bad.p);
+            HIPCHK(hipGetLastError());
+            if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); t_hook += sw.lap(); }
+        }
+    }
+    unsigned bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, d_bad.p, sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    if (bad) return BVG_E_EOF;                                              // a successor outside [0, n): malformed stream
+    sw.lap();
+    uint64_t count = 0;
+    rc = number_t<T>(g, d_parent, flags, comp, sizes, sizes_cap, n_components, dev, &count);
+    if (rc && rc != BVG_E_CAPACITY) return rc;
     if (dbgt) fprintf(stderr, "[bvg] components: plan %.1f ms (%zu batches of <= %llu arcs, %llu arcs), decode %.1f ms, hook %.1f ms, finish %.1f ms (%llu components)\n",
                       t_plan, sp.batches.size(), (unsigned long long)per, (unsigned long long)sp.arcs, t_dec, t_hook, sw.lap(), (unsigned long long)count);
-    return cap_ok ? 0 : BVG_E_CAPACITY;
+    return rc;
 }
 
 int components_impl(bvg_graph* g, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components, bool dev) {
@@ -270,6 +281,14 @@ int components_impl(bvg_graph* g, uint32_t flags, int64_t* comp, int64_t* sizes,
 }
 
 }  // namespace
+
+namespace bvghost {
+int number_components(bvg_graph* g, void* d_parent, bool wide, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components, bool dev,
+                      uint64_t* count_out) {
+    return wide ? number_t<uint64_t>(g, (uint64_t*)d_parent, flags, comp, sizes, sizes_cap, n_components, dev, count_out)
+                : number_t<uint32_t>(g, (uint32_t*)d_parent, flags, comp, sizes, sizes_cap, n_components, dev, count_out);
+}
+}  // namespace bvghost
 
 int bvg_components(bvg_graph* g, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components) {
     return guarded([&] { return components_impl(g, flags, comp, sizes, sizes_cap, n_components, false); });

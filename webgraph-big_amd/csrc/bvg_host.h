@@ -280,6 +280,13 @@ struct SweepPlan {
     int decode(bvg_graph* g, const Batch& b) const;
 };
 
+// ---- bvg_components.hip: the numbering that bvg_components and bvg_scc share.  d_parent (uint32 per node, uint64 when `wide`) holds trees whose roots
+// are the smallest nodes of their components (bvg_scc: parent[x] is that node already).  comp[x] = the rank of x's root among the roots; sizes and,
+// with BVG_CC_SORT_BY_SIZE in `flags`, the renumbering by decreasing size, as bvg_components documents them.  Needs 12 bytes per node of its own.
+// Returns 0 or BVG_E_CAPACITY (sizes_cap below the count: comp and the count are written all the same); *count_out: the count.
+int number_components(bvg_graph* g, void* d_parent, bool wide, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components, bool dev,
+                      uint64_t* count_out);
+
 // ---- bvg_api.hip: what bvg_successors_batch and the frontier route of bvg_bfs_visit share (described there)
 int decode_range_impl(bvg_graph* g, int64_t from, int64_t to, int32_t* outdeg, int64_t* succ, uint64_t cap, uint64_t* n_succ, bool dev, bool narrow = false);
 constexpr int64_t kMaxBatchRequests = 0x3FFFFFFF;

@@ -178,6 +178,8 @@ public:
         if (sizes) sizes->resize((size_t)count);
         return (int64_t)count;
     }
+    // strongly connected components (algo/StronglyConnectedComponents.java) on the device: the class is below
+    inline class StronglyConnectedComponents stronglyConnectedComponents(bool computeBuckets = false);
     // breadth-first visits on the device (algo/ParallelBreadthFirstVisit.java): the class is below
     inline class ParallelBreadthFirstVisit breadthFirstVisit(bool parent = false);
     // HyperBall on the device (algo/HyperBall.java, standard iterations): the class is below
@@ -195,6 +197,44 @@ public:
         bvg_scan_result r; check(bvg_scan(h_, from, to < 0 ? p_.nodes : to, &r), "scan"); return r;
     }
 };
+
+// StronglyConnectedComponents (algo/StronglyConnectedComponents.java) over bvg_scc: what compute() leaves -- numberOfComponents, component[]
+// and, with computeBuckets, buckets[] (one byte per node, 0 / 1) -- plus computeSizes() and sortBySize().  The partition, the count, the
+// sizes and the buckets are the reference's; the numbering is by smallest node, not Tarjan's emission order (include/bvgraph_hip.h).
+class StronglyConnectedComponents {
+    std::shared_ptr<BVGraph> g_;
+    void run(uint32_t flags, std::vector<int64_t>* sizes) {
+        const size_t n = (size_t)g_->numNodes();
+        component.resize(n);
+        if (sizes) sizes->resize(n ? n : 1);                                                // (there are at most n components)
+        if (hasBuckets) buckets.resize(n ? n : 1);
+        uint64_t count = 0;
+        check(bvg_scc(g_->handle(), flags | (hasBuckets ? BVG_SCC_BUCKETS : 0u), n ? component.data() : nullptr, sizes ? sizes->data() : nullptr,
+                      sizes ? (uint64_t)sizes->size() : 0, &count, hasBuckets ? buckets.data() : nullptr, counters), "scc");
+        if (sizes) sizes->resize((size_t)count);
+        if (hasBuckets) buckets.resize(n);
+        numberOfComponents = (int64_t)count;
+    }
+public:
+    int64_t numberOfComponents = 0;
+    std::vector<int64_t> component;
+    std::vector<uint8_t> buckets; bool hasBuckets = false;
+    uint64_t counters[BVG_SCC_COUNTERS] = {};
+    StronglyConnectedComponents(std::shared_ptr<BVGraph> g, bool computeBuckets) : g_(std::move(g)), hasBuckets(computeBuckets) { run(0u, nullptr); }
+    // the size of every component, in the numbering component[] has now
+    std::vector<int64_t> computeSizes() {
+        std::vector<int64_t> sizes((size_t)numberOfComponents, 0);
+        for (int64_t c : component) sizes[(size_t)c]++;
+        return sizes;
+    }
+    // renumbers component[] by decreasing size (ties: smallest node first) and returns the sizes in the new order
+    std::vector<int64_t> sortBySize() {
+        std::vector<int64_t> sizes;
+        run(BVG_SCC_SORT_BY_SIZE, &sizes);
+        return sizes;
+    }
+};
+inline StronglyConnectedComponents BVGraph::stronglyConnectedComponents(bool computeBuckets) { return StronglyConnectedComponents(shared_from_this(), computeBuckets); }
 
 // ParallelBreadthFirstVisit (algo/ParallelBreadthFirstVisit.java) over bvg_bfs_*: marker / round / queue / cutPoints live on the device
 // between visits; inside a level the queue is in increasing id, and with parent = true a node's parent is the smallest node of the
