@@ -246,6 +246,34 @@ int bvg_scc(bvg_graph* g, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_
 int bvg_scc_dev(bvg_graph* g, uint32_t flags, void* d_comp, void* d_sizes, uint64_t sizes_cap,
                 uint64_t* n_components, void* d_buckets, uint64_t* counters);
 
+/* ---- exact geometric centralities (algo/LinearGeometricCentrality.java) ----
+ * centrality[s - from] = sum over the nodes y reachable from s of coeff(d(s, y)), s itself included with coeff(0), and reachable[s - from] =
+ * the number of those nodes (s included), for the sources s in [from, to): what the reference computes with one breadth-first visit per
+ * source.  Here 64 W consecutive sources (W = 1, 2, 4 or 8 64-bit words per node) advance together, one bit each, and ONE sweep of the
+ * compressed graph moves all of them by one level.  coeff by `kind`:
+ *   BVG_GEO_HARMONIC     d == 0 ? 0 : 1 / d                     (HarmonicCoefficients)
+ *   BVG_GEO_POWER_LAW    pow(d, param)                          (PowerLawCoefficients; param < 0: coeff(0) = +inf and so is every value)
+ *   BVG_GEO_EXPONENTIAL  pow(param, d)                          (ExponentialCoefficients)
+ *   BVG_GEO_TABLE        table[d] for d < table_len, 0 beyond   (any finite-support centrality; the visits still run to their end)
+ * THE ROUNDING IS NOT THE REFERENCE'S: it adds coeff to a float once per discovered node (one float rounding per reached node); here
+ * coeff(d) times the number of nodes at distance d is summed over d in double and rounded to float once -- the reference's value up to
+ * that accumulated float error, and closer to the exact sum.
+ * centrality (float) and reachable (int64) hold to - from elements; either may be NULL.  hist (may be NULL): hist[d] = the number of
+ * (source, node) pairs at distance d (hist[0] = to - from), *hist_len (required with hist) = distances present; hist_cap below that:
+ * BVG_E_CAPACITY, *hist_len and the other outputs written all the same.  counters (may be NULL): out[BVG_GEO_COUNTERS] = passes, sweeps,
+ * batch decodes, words per node, levels of the deepest pass, levels skipped without atomics (0: not built), 1 if a single resident batch
+ * was used, reserved.  Device memory: 24 W bytes per node, one arc-bounded batch of the decode, O(64 W) accumulators; BVG_E_NOMEM leaves g
+ * usable.  g NULL, unknown kind, BVG_GEO_TABLE without a table or with table_len 0, from > to or a range outside [0, nodes], hist without
+ * hist_len, node_base != 0: BVG_E_ARG, checked before any device call.  An empty range succeeds and writes nothing.  Malformed streams
+ * report the decode's status (a successor outside [0, nodes): BVG_E_EOF, never used as an index).  _dev: centrality / reachable in device
+ * memory, hist and counters on the host. */
+enum { BVG_GEO_HARMONIC = 0, BVG_GEO_POWER_LAW = 1, BVG_GEO_EXPONENTIAL = 2, BVG_GEO_TABLE = 3 };
+#define BVG_GEO_COUNTERS 8
+int bvg_geometric(bvg_graph* g, int kind, double param, const double* table, uint64_t table_len, int64_t from, int64_t to,
+                  float* centrality, int64_t* reachable, uint64_t* hist, uint64_t hist_cap, uint64_t* hist_len, uint64_t* counters);
+int bvg_geometric_dev(bvg_graph* g, int kind, double param, const double* table, uint64_t table_len, int64_t from, int64_t to,
+                      void* d_centrality, void* d_reachable, uint64_t* hist, uint64_t hist_cap, uint64_t* hist_len, uint64_t* counters);
+
 /* ---- breadth-first visits (algo/ParallelBreadthFirstVisit.java) ----
  * A visit object keeps on the device what the reference's class keeps (ParallelBreadthFirstVisit.java:79-148): marker[nodes] (-1 = not
  * enqueued yet; otherwise the round in which the node was reached, or its parent with BVG_BFS_PARENT), the round counter (-1 before the

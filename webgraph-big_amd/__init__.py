@@ -15,4 +15,5 @@ from .bvgraph import (BVGraph, NodeIterator, LazyLongIterator, BVGraphError, Ill
                       CC_SORT_BY_SIZE, ComponentsResult, store_components, load_components, components_main,
                       BFS_PARENT, BFS_COUNTERS, BreadthFirstVisit,
                       SCC_SORT_BY_SIZE, SCC_BUCKETS, SCC_COUNTERS, SCCResult, store_scc, load_scc, scc_main,
+                      GEO_COUNTERS, GeometricResult, parse_coefficients_spec, store_geometric, load_geometric, geometric_main,
                       HB_SUM_OF_DISTANCES, HB_HARMONIC, HyperBall, hyperball_main, store_floats, load_floats)

@@ -78,6 +78,17 @@ def scc_signatures():
     return {"bvg_scc": list(args), "bvg_scc_dev": list(args)}
 
 
+# the `kind` of bvg_geometric (BVG_GEO_HARMONIC, ...) / the number of words it writes to `counters` (BVG_GEO_COUNTERS)
+GEO_HARMONIC, GEO_POWER_LAW, GEO_EXPONENTIAL, GEO_TABLE, GEO_COUNTER_WORDS = 0, 1, 2, 3, 8
+
+
+def geometric_signatures():
+    """argtypes of bvg_geometric / bvg_geometric_dev (exact geometric centralities), by name."""
+    vp, i64, u64 = C.c_void_p, C.c_int64, C.c_uint64
+    args = [vp, C.c_int, C.c_double, vp, u64, i64, i64, vp, vp, vp, u64, C.POINTER(u64), vp]
+    return {"bvg_geometric": list(args), "bvg_geometric_dev": list(args)}
+
+
 OK, E_ARG, E_STATE, E_UNSUPPORTED, E_IO, E_EOF, E_NOMEM, E_HIP, E_CAPACITY = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 

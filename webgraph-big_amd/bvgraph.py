@@ -195,6 +195,36 @@ def _scc_fns():
     return L
 
 
+def _geometric_fns():
+    """bvg_geometric / bvg_geometric_dev, bound on first use (as _components_fns)."""
+    L = lib()
+    if getattr(L, "_geo_bound", False):
+        return L
+    for name, args in _abi.geometric_signatures().items():
+        if not hasattr(L, name):
+            raise UnsupportedOperationException(_abi.E_UNSUPPORTED, name + " is not in this build of the library")
+        getattr(L, name).argtypes = args
+    L._geo_bound = True
+    return L
+
+
+def _geometric_coeffs(coeffs):
+    """(kind, param, table or None) of what linear_geometric_centrality takes: "harmonic", ("power", e), ("exp", b) or an array."""
+    if isinstance(coeffs, str):
+        if coeffs == "harmonic":
+            return _abi.GEO_HARMONIC, 0.0, None
+        raise IllegalArgumentException(_abi.E_ARG, "unknown coefficients %r" % (coeffs,))
+    if isinstance(coeffs, tuple) and len(coeffs) == 2 and isinstance(coeffs[0], str):
+        kind = {"power": _abi.GEO_POWER_LAW, "exp": _abi.GEO_EXPONENTIAL}.get(coeffs[0])
+        if kind is None:
+            raise IllegalArgumentException(_abi.E_ARG, "unknown coefficients %r" % (coeffs,))
+        return kind, float(coeffs[1]), None
+    table = np.ascontiguousarray(coeffs, dtype=np.float64)
+    if table.ndim != 1 or len(table) == 0:
+        raise IllegalArgumentException(_abi.E_ARG, "a coefficient table is a non-empty one-dimensional array")
+    return _abi.GEO_TABLE, 0.0, table
+
+
 def _hyperball_fns():
     """The bvg_hyperball_* entry points, bound on first use (as _bfs_fns)."""
     L = lib()
@@ -873,6 +903,57 @@ class BVGraph:
         _check(st, "strongly_connected_components_dev")
         return int(cnt.value), dict(zip(SCC_COUNTERS, (int(v) for v in ctr)))
 
+    def _geometric_range(self, sources):
+        n = self.num_nodes()
+        lo, hi = (0, n) if sources is None else (int(sources[0]), int(sources[1]))
+        if lo < 0 or lo > hi or hi > n:
+            raise IllegalArgumentException(_abi.E_ARG, "sources [%d, %d) of a graph of %d nodes" % (lo, hi, n))
+        return lo, hi
+
+    def linear_geometric_centrality(self, coeffs, sources=None, histogram=False):
+        """LinearGeometricCentrality.compute (algo/LinearGeometricCentrality.java) on the device (bvg_geometric): the exact positive
+        geometric centrality sum of coeff(d(s, y)) over the nodes y reachable from s, and the number of those nodes (s included), for
+        the sources s in `sources` = (from, to) (None: every node), by bit-parallel breadth-first visits: one sweep of the compressed
+        graph advances up to 512 sources by one level.  coeffs: "harmonic" (0, 1, 1/2, ...), ("power", e) (d ** e), ("exp", b)
+        (b ** d) or an array (coeff(d) = array[d], 0 beyond its end).  The sum is formed in double and rounded to float32 once (the
+        reference rounds once per reached node).  histogram=True also returns the number of (source, node) pairs at every distance.
+        Returns a GeometricResult."""
+        L = _geometric_fns()
+        kind, param, table = _geometric_coeffs(coeffs)
+        lo, hi = self._geometric_range(sources)
+        cen = np.empty(hi - lo, dtype=np.float32); rea = np.empty(hi - lo, dtype=np.int64)
+        ctr = np.zeros(_abi.GEO_COUNTER_WORDS, dtype=np.uint64)
+        cap = self.num_nodes() + 1 if histogram else 0                      # (distances are below the number of nodes)
+        hist = np.zeros(cap, dtype=np.uint64) if histogram else None
+        hlen = C.c_uint64(0)
+        _check(L.bvg_geometric(self._h, kind, param, None if table is None else table.ctypes.data, 0 if table is None else len(table), lo, hi,
+                               cen.ctypes.data if hi > lo else None, rea.ctypes.data if hi > lo else None, None if hist is None else hist.ctypes.data, cap,
+                               C.byref(hlen), ctr.ctypes.data), "linear_geometric_centrality")
+        return GeometricResult(cen, rea, None if hist is None else hist[:int(hlen.value)].copy(), dict(zip(GEO_COUNTERS, (int(v) for v in ctr))), (lo, hi), (kind, param))
+
+    linearGeometricCentrality = linear_geometric_centrality
+
+    def linear_geometric_centrality_dev(self, coeffs, centrality_tensor=None, reachable_tensor=None, sources=None, histogram=False):
+        """bvg_geometric_dev: the centralities into centrality_tensor (float32) and the reachable counts into reachable_tensor (int64),
+        each of at least to - from elements on the graph's device; either may be None.  Returns (histogram or None, counters)."""
+        import torch
+        L = _geometric_fns()
+        kind, param, table = _geometric_coeffs(coeffs)
+        lo, hi = self._geometric_range(sources)
+        for t, what, dt in ((centrality_tensor, "centrality", torch.float32), (reachable_tensor, "reachable", torch.int64)):
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
+                raise IllegalArgumentException(_abi.E_ARG, "%s must be a contiguous %s CUDA tensor" % (what, dt))
+            if t is not None and t.numel() < hi - lo:
+                raise IllegalArgumentException(_abi.E_ARG, "%s holds %d elements, the range %d sources" % (what, t.numel(), hi - lo))
+        ctr = np.zeros(_abi.GEO_COUNTER_WORDS, dtype=np.uint64)
+        cap = self.num_nodes() + 1 if histogram else 0
+        hist = np.zeros(cap, dtype=np.uint64) if histogram else None
+        hlen = C.c_uint64(0)
+        _check(L.bvg_geometric_dev(self._h, kind, param, None if table is None else table.ctypes.data, 0 if table is None else len(table), lo, hi,
+                                   None if centrality_tensor is None else centrality_tensor.data_ptr(), None if reachable_tensor is None else reachable_tensor.data_ptr(),
+                                   None if hist is None else hist.ctypes.data, cap, C.byref(hlen), ctr.ctypes.data), "linear_geometric_centrality_dev")
+        return None if hist is None else hist[:int(hlen.value)].copy(), dict(zip(GEO_COUNTERS, (int(v) for v in ctr)))
+
     def breadth_first_visit(self, parent=False):
         """ParallelBreadthFirstVisit (algo/ParallelBreadthFirstVisit.java) with its state on the device: see BreadthFirstVisit."""
         return BreadthFirstVisit(self, parent)
@@ -916,6 +997,7 @@ CC_SORT_BY_SIZE = 1
 BFS_PARENT = 1
 SCC_SORT_BY_SIZE, SCC_BUCKETS = 1, 2
 SCC_COUNTERS = ("sweeps", "batch_decodes", "trim_passes", "trimmed_nodes", "fwbw_component", "colouring_rounds", "colouring_components", "single_resident_batch")
+GEO_COUNTERS = ("passes", "sweeps", "batch_decodes", "words_per_node", "deepest_pass_levels", "levels_skipped", "single_resident_batch", "reserved")
 BFS_COUNTERS = ("frontier_levels", "sweep_levels", "deep_requests", "frontier_batches", "sweep_batches", "sorted_levels", "compacted_levels", "first_level_route")
 
 
@@ -1362,6 +1444,116 @@ def scc_main(argv=None):
         g.close()
     store_scc(r, out)
     print("%d components" % r.count)
+    return r
+
+
+class GeometricResult:
+    """What LinearGeometricCentrality holds after compute(), for the sources [from, to): centrality (float32) and reachable (int64) per
+    source, the distance histogram over those sources (uint64, or None) and the counters of bvg_geometric by name (GEO_COUNTERS).
+    A result computed with ("power", 1) holds the sum of the distances from every source: closeness() and lin() derive the two
+    centralities from it by the formulas of bvg_hyperball_centrality (HyperBall.main)."""
+
+    def __init__(self, centrality, reachable, histogram=None, counters=None, sources=None, coefficients=None):
+        self.centrality, self.reachable, self.histogram, self.counters = centrality, reachable, histogram, counters or {}
+        self.sources = sources if sources is not None else (0, len(centrality))
+        self.coefficients = coefficients
+
+    def _sum_of_distances(self):
+        if self.coefficients != (_abi.GEO_POWER_LAW, 1.0):
+            raise IllegalStateException(_abi.E_STATE, 'closeness and Lin need the sum of distances: coefficients ("power", 1)')
+        return np.asarray(self.centrality, dtype=np.float64)
+
+    def closeness(self):
+        """1 / (the sum of the distances), 0 where that sum is 0."""
+        d = self._sum_of_distances()
+        return np.where(d == 0, 0.0, 1.0 / np.where(d == 0, 1.0, d)).astype(np.float32)
+
+    def lin(self):
+        """reachable^2 / (the sum of the distances), 1 where that sum is 0."""
+        d = self._sum_of_distances()
+        r = np.asarray(self.reachable, dtype=np.float64)
+        return np.where(d == 0, 1.0, r * r / np.where(d == 0, 1.0, d)).astype(np.float32)
+
+    def neighbourhood_function(self):
+        """The running sums of the histogram: the pairs (source, node) at distance at most t."""
+        if self.histogram is None:
+            raise IllegalStateException(_abi.E_STATE, "computed without histogram=True")
+        return np.cumsum(self.histogram.astype(np.uint64))
+
+    def __repr__(self):
+        return "GeometricResult(sources=[%d, %d), histogram=%s)" % (self.sources[0], self.sources[1], "yes" if self.histogram is not None else "no")
+
+
+_GEO_SPEC_PREFIX = "it.unimi.dsi.big.webgraph.algo.LinearGeometricCentrality"
+
+
+def parse_coefficients_spec(spec):
+    """The coefficientsSpec of LinearGeometricCentrality.main -- CLASSNAME or CLASSNAME(arg) -- as what linear_geometric_centrality
+    takes: HarmonicCoefficients, PowerLawCoefficients(x), ExponentialCoefficients(x), bare or with the reference's class-name prefix
+    (it.unimi.dsi.big.webgraph.algo.LinearGeometricCentrality$ or the same with a dot)."""
+    import re
+    m = re.fullmatch(r"\s*([A-Za-z_$.][\w$.]*?)\s*(?:\((.*)\))?\s*", spec)
+    if not m:
+        raise IllegalArgumentException(_abi.E_ARG, "malformed coefficients spec %r" % (spec,))
+    name, args = m.group(1), m.group(2)
+    for sep in ("$", "."):
+        if name.startswith(_GEO_SPEC_PREFIX + sep):
+            name = name[len(_GEO_SPEC_PREFIX) + 1:]
+    argv = [] if args is None or not args.strip() else [a.strip() for a in args.split(",")]
+    try:
+        vals = [float(a) for a in argv]
+    except ValueError:
+        raise IllegalArgumentException(_abi.E_ARG, "malformed coefficients spec %r" % (spec,))
+    if name == "HarmonicCoefficients" and not vals:
+        return "harmonic"
+    if name == "PowerLawCoefficients" and len(vals) == 1:
+        return ("power", vals[0])
+    if name == "ExponentialCoefficients" and len(vals) == 1:
+        return ("exp", vals[0])
+    raise IllegalArgumentException(_abi.E_ARG, "unknown coefficients class or arguments in %r" % (spec,))
+
+
+def store_geometric(result, centrality_filename, reachable_filename):
+    """LinearGeometricCentrality.main's output files: the centralities as BinIO.storeFloats writes them (big-endian float32) and the
+    reachable counts as BinIO.storeLongs does (big-endian int64), no headers.  Returns the paths written."""
+    np.asarray(result.centrality, dtype=">f4").tofile(centrality_filename)
+    np.asarray(result.reachable, dtype=">i8").tofile(reachable_filename)
+    return [centrality_filename, reachable_filename]
+
+
+def load_geometric(centrality_filename, reachable_filename):
+    """Reads back what store_geometric wrote: (centrality float32, reachable int64)."""
+    return np.fromfile(centrality_filename, dtype=">f4").astype(np.float32), np.fromfile(reachable_filename, dtype=">i8").astype(np.int64)
+
+
+def geometric_arg_parser():
+    """The command line of LinearGeometricCentrality.main: [-m] [-T n] graphBasename coefficientsSpec centralityFilename reachableFilename."""
+    import argparse
+    ap = argparse.ArgumentParser(prog="geometric", description="Exact positive linear geometric centrality of a BVGraph, computed on the device.")
+    ap.add_argument("-m", "--mapped", action="store_true", help="(accepted and ignored: the graph lives in device memory)")
+    ap.add_argument("-T", "--threads", type=int, default=0, help="(accepted and ignored)")
+    ap.add_argument("--device", type=int, default=0, help="the GPU to run on")
+    ap.add_argument("graphBasename", help="the basename of the graph")
+    ap.add_argument("coefficientsSpec", help="HarmonicCoefficients, PowerLawCoefficients(x) or ExponentialCoefficients(x)")
+    ap.add_argument("centralityFilename", help="where the centrality scores are stored (big-endian floats)")
+    ap.add_argument("reachableFilename", help="where the numbers of reachable nodes are stored (big-endian longs)")
+    return ap
+
+
+def geometric_main(argv=None):
+    """LinearGeometricCentrality.main: loads graphBasename, computes the centrality of every node, writes the two files."""
+    ap = geometric_arg_parser()
+    args = ap.parse_args(argv)
+    try:
+        coeffs = parse_coefficients_spec(args.coefficientsSpec)
+    except IllegalArgumentException as e:
+        ap.error(str(e))
+    g = BVGraph.load(args.graphBasename, device=args.device)
+    try:
+        r = g.linear_geometric_centrality(coeffs)
+    finally:
+        g.close()
+    store_geometric(r, args.centralityFilename, args.reachableFilename)
     return r
 
 

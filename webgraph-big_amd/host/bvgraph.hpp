@@ -180,6 +180,8 @@ public:
     }
     // strongly connected components (algo/StronglyConnectedComponents.java) on the device: the class is below
     inline class StronglyConnectedComponents stronglyConnectedComponents(bool computeBuckets = false);
+    // exact geometric centralities on the device (algo/LinearGeometricCentrality.java): the class and the coefficient objects are below
+    template <typename Coeffs> inline class LinearGeometricCentrality linearGeometricCentrality(const Coeffs& coeffs);
     // breadth-first visits on the device (algo/ParallelBreadthFirstVisit.java): the class is below
     inline class ParallelBreadthFirstVisit breadthFirstVisit(bool parent = false);
     // HyperBall on the device (algo/HyperBall.java, standard iterations): the class is below
@@ -235,6 +237,39 @@ public:
     }
 };
 inline StronglyConnectedComponents BVGraph::stronglyConnectedComponents(bool computeBuckets) { return StronglyConnectedComponents(shared_from_this(), computeBuckets); }
+
+// The coefficient objects of LinearGeometricCentrality (LinearGeometricCentrality.java:82-124): get(d) is what the library evaluates.
+struct HarmonicCoefficients { double get(int64_t d) const { return d == 0 ? 0.0 : 1.0 / (double)d; } };
+struct PowerLawCoefficients { double exponent; explicit PowerLawCoefficients(double e) : exponent(e) {} };
+struct ExponentialCoefficients { double base; explicit ExponentialCoefficients(double b) : base(b) {} };
+
+// LinearGeometricCentrality (algo/LinearGeometricCentrality.java) over bvg_geometric: compute() fills centrality[] (float) and reachable[]
+// for every node, or for the sources [from, to) given to it.  Coefficients: one of the three objects above or a std::vector<double> (coeff(d)
+// = v[d], 0 beyond its end).  The sum is formed in double and rounded to float once; the reference rounds once per reached node.
+class LinearGeometricCentrality {
+    std::shared_ptr<BVGraph> g_;
+    int kind_; double param_ = 0; std::vector<double> table_;
+public:
+    std::vector<float> centrality;
+    std::vector<int64_t> reachable;
+    std::vector<uint64_t> histogram;                                                        // pairs (source, node) by distance, over the sources of the last compute()
+    uint64_t counters[BVG_GEO_COUNTERS] = {};
+    LinearGeometricCentrality(std::shared_ptr<BVGraph> g, const HarmonicCoefficients&) : g_(std::move(g)), kind_(BVG_GEO_HARMONIC) {}
+    LinearGeometricCentrality(std::shared_ptr<BVGraph> g, const PowerLawCoefficients& c) : g_(std::move(g)), kind_(BVG_GEO_POWER_LAW), param_(c.exponent) {}
+    LinearGeometricCentrality(std::shared_ptr<BVGraph> g, const ExponentialCoefficients& c) : g_(std::move(g)), kind_(BVG_GEO_EXPONENTIAL), param_(c.base) {}
+    LinearGeometricCentrality(std::shared_ptr<BVGraph> g, const std::vector<double>& table) : g_(std::move(g)), kind_(BVG_GEO_TABLE), table_(table) {}
+    void compute() { compute(0, g_->numNodes()); }
+    void compute(int64_t from, int64_t to) {
+        const size_t count = to > from ? (size_t)(to - from) : 0;
+        centrality.assign(count, 0.0f); reachable.assign(count, 0);
+        histogram.assign((size_t)g_->numNodes() + 1, 0);                                    // (distances are below the number of nodes)
+        uint64_t len = 0;
+        check(bvg_geometric(g_->handle(), kind_, param_, table_.empty() ? nullptr : table_.data(), (uint64_t)table_.size(), from, to, count ? centrality.data() : nullptr,
+                            count ? reachable.data() : nullptr, histogram.data(), (uint64_t)histogram.size(), &len, counters), "linearGeometricCentrality");
+        histogram.resize((size_t)len);
+    }
+};
+template <typename Coeffs> inline LinearGeometricCentrality BVGraph::linearGeometricCentrality(const Coeffs& coeffs) { return LinearGeometricCentrality(shared_from_this(), coeffs); }
 
 // ParallelBreadthFirstVisit (algo/ParallelBreadthFirstVisit.java) over bvg_bfs_*: marker / round / queue / cutPoints live on the device
 // between visits; inside a level the queue is in increasing id, and with parent = true a node's parent is the smallest node of the
