@@ -375,7 +375,8 @@ enum { BVG_LABEL_GAMMA_INT = 1, BVG_LABEL_FIXED_INT = 2, BVG_LABEL_FIXED_INT_LIS
 typedef struct bvg_labels bvg_labels;
 /* Label.toSpec() text, e.g. "it.unimi.dsi.big.webgraph.labelling.FixedWidthIntLabel(FOO,10)" -> kind, width. */
 int bvg_labels_parse_spec(const char* spec, int* kind, int* width);
-/* label_offsets: nodes+1 bit positions into the label stream (decode basename.labeloffsets with bvg_decode_offsets(.., BVG_GAMMA, ..)). */
+/* label_offsets: nodes+1 bit positions into the label stream (decode basename.labeloffsets with bvg_decode_offsets(.., BVG_GAMMA, ..)).
+ * BVG_E_EOF if the last one lies behind the stream, else BVG_E_IO if they are not non-decreasing; no handle is returned then. */
 int bvg_labels_open_mem(int kind, int width, int64_t nodes, const uint8_t* stream, uint64_t nbytes, const uint64_t* label_offsets, int device, bvg_labels** out);
 /* basename.properties alone (host-only): label class and the basename of the underlying graph (property underlyinggraph,
  * resolved against the property file, :95-97). */
@@ -388,16 +389,21 @@ void bvg_labels_close(bvg_labels* l);
 int bvg_labels_info(const bvg_labels* l, int* kind, int* width, int64_t* nodes, uint64_t* stream_bytes);
 /* Labels of the arcs of nodes [from,to) in the order bvg_decode_range lists the successors; outdeg[to-from] as returned by it.
  * *n_labels = sum of the outdegrees; BVG_E_CAPACITY if cap is smaller; BVG_E_EOF if a node's run does not end at the next offset
- * (the outdegrees do not belong to this label stream). */
+ * (the outdegrees do not belong to this label stream, or the stream is damaged), and if a gamma-coded label is 2^31 or more:
+ * GammaCodedIntLabel cannot write such a value, the reference's readGamma() would wrap it to a negative int, and a negative label
+ * handed on silently is worse than an error.  `labels` is written only when the call returns 0. */
 int bvg_labels_decode_range(bvg_labels* l, int64_t from, int64_t to, const int32_t* outdeg, int32_t* labels, uint64_t cap, uint64_t* n_labels);
 /* List labels (kind BVG_LABEL_FIXED_INT_LIST): list_off[arcs+1] = exclusive prefix of the list lengths of the arcs of [from,to) in
  * successor order, values[cap] = the concatenated elements; *n_values = their number.  BVG_E_CAPACITY if cap is smaller (list_off is
- * filled either way: size the buffer from list_off[arcs] and call again). */
+ * filled either way: size the buffer from list_off[arcs] and call again).  BVG_E_EOF as for bvg_labels_decode_range; a gamma-coded
+ * list LENGTH of 2^31 or more is refused in the same way (readGamma() is an int).  Next to BVG_E_EOF `values` is not written, and
+ * list_off counts every list that cannot be read inside its node's run as empty, along with the lists behind it in that node. */
 int bvg_labels_decode_range_lists(bvg_labels* l, int64_t from, int64_t to, const int32_t* outdeg, uint64_t* list_off, int32_t* values, uint64_t cap, uint64_t* n_values);
 /* The same for FixedWidthLongListLabel (labelling/FixedWidthLongListLabel.java:81-87: gamma(length), then readLong(width), width <= 64):
  * kind BVG_LABEL_FIXED_LONG_LIST, 64-bit elements. */
 int bvg_labels_decode_range_lists64(bvg_labels* l, int64_t from, int64_t to, const int32_t* outdeg, uint64_t* list_off, int64_t* values, uint64_t cap, uint64_t* n_values);
-/* Same as bvg_labels_decode_range, outdegrees (int32) and labels (int32) in device memory: chains with bvg_decode_range_dev without leaving HBM. */
+/* Same as bvg_labels_decode_range, outdegrees (int32) and labels (int32) in device memory: chains with bvg_decode_range_dev without leaving HBM.
+ * Next to BVG_E_CAPACITY nothing is written; next to BVG_E_EOF d_labels[0, *n_labels) holds no labels to be used. */
 int bvg_labels_decode_range_dev(bvg_labels* l, int64_t from, int64_t to, const void* d_outdeg, void* d_labels, uint64_t cap, uint64_t* n_labels);
 
 /* ---- the compressor on the device (second half): BVGraph.store (BVG:2329-2470; CompressionThread.call

@@ -159,6 +159,46 @@ def test_compressor_input_check_under_address_sanitizer():
                               LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1")
 
 
+# what of tests/test_gpu_labels.py each lane order runs here (the GPU run has all of it)
+LABELS_ON_THE_EMULATOR = {
+    "fwd": "not parameter_space or random",
+    "rev": "prefix_sum or ranges_on_one_handle or workspace_reuse or end_of_stream or capacity or dev_entry",
+}
+# the streams that are wrong, and the streams that end on the last bit of the file: what the kernels read at and behind the end of a stream
+LABELS_UNDER_ASAN = "defect or hand_assembled or end_of_stream or files_that_are_wrong"
+
+
+@pytest.mark.parametrize("order", ["fwd", "rev"])
+def test_arc_label_suite_on_the_emulator(emu_lib, order):
+    """tests/test_gpu_labels.py -- the arc-label decoder against the plain model of tests/labels_model.py -- on the CPU.  The label kernels have no
+    cross-lane traffic, but the prefix sum they share with the decoder (csrc/bvg_kernels.hip: scan_partials, scan_partials_serial, scan_final) adds up
+    across the lanes of a wavefront and through LDS behind a __syncthreads(), so both lane orders run: the forward order everything kept, the reversed
+    order the tests that vary the number of nodes and arcs that are scanned.  Cut from the emulated selection, for time only (all of it runs on the GPU):
+    three of the four value patterns of the sweep over every width (test_parameter_space: 1 - 2.6 s per class and pattern here).  The status-parity cases
+    (every defect, the hand-assembled codes), the end-of-stream cases and the file cases run here in full, before any GPU sees them.
+    Measured on one machine, next to the figures of test_offsets_derivation_suite_on_the_emulator: the whole file 33 s; this selection 19 s (fwd) +
+    9 s (rev), the randomised test below 1.5 s per order: 32 s together."""
+    _gpu_file_on_the_emulator(emu_lib, order, [os.path.join(ROOT, "tests", "test_gpu_labels.py"), "-k", LABELS_ON_THE_EMULATOR[order]])
+
+
+@pytest.mark.parametrize("order,first", [("fwd", 0), ("rev", 10)])
+def test_randomised_arc_labels_on_the_emulator(emu_lib, order, first):
+    """tests/test_gpu_labels_fuzz.py, ten cases per lane order (13 ms a case here); the two orders run different cases."""
+    _gpu_file_on_the_emulator(emu_lib, order, [os.path.join(ROOT, "tests", "test_gpu_labels_fuzz.py")], BVG_LABELS_FUZZ=str(first + 10), BVG_LABELS_FUZZ_FROM=str(first))
+
+
+@pytest.mark.skipif(not os.environ.get("BVG_EMU_ASAN"), reason="opt-in (BVG_EMU_ASAN=1): the AddressSanitizer build of the emulated library takes ~4 minutes to compile")
+def test_arc_labels_of_wrong_streams_under_address_sanitizer():
+    """The status-parity cases of tests/test_gpu_labels.py -- truncated streams, flipped bits, degrees off by one, an all-zero stream, gamma codes of 64 zeros
+    and more, list lengths without elements -- and the streams that end on the last bit of the file, under ASan + UBSan, before they go to a GPU:
+    BitCursor::peek_global loads nine bytes from the byte of every position (clamped to the last 16 bytes of the padded copy), and a read behind the copy
+    is silent on the hardware."""
+    subprocess.check_call(["make", "-s", "-j4", "-C", EMU, "asan"])
+    asan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"], text=True).strip()
+    _gpu_file_on_the_emulator(os.path.join(EMU, "libbvgraph_emu_asan.so"), "fwd", [os.path.join(ROOT, "tests", "test_gpu_labels.py"), "-k", LABELS_UNDER_ASAN],
+                              LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1")
+
+
 def test_randomised_parity_of_the_lean_kernels_on_the_emulator(emu_lib):
     """tests/emu/fuzz_flat.py: random shapes, windows, reference-chain depths, interval lengths, zeta k, LDS geometries (small pools: sub-rows and compaction), records per
     super-row and lane orders; scan_kernel and the experimental flat kernel against the oracle (8 cases here; 90 ran on the final round-5 tree: BVG_EMU_FUZZ=<n> for more)."""

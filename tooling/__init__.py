@@ -245,7 +245,7 @@ class StoredLabels:
         self.kind, self.width, self.stream, self.offsets = kind, width, stream, offsets
 
     def spec(self):
-        cls = "it.unimi.dsi.big.webgraph.labelling." + {1: "GammaCodedIntLabel", 2: "FixedWidthIntLabel", 3: "FixedWidthIntListLabel"}[self.kind]
+        cls = "it.unimi.dsi.big.webgraph.labelling." + {1: "GammaCodedIntLabel", 2: "FixedWidthIntLabel", 3: "FixedWidthIntListLabel", 4: "FixedWidthLongListLabel"}[self.kind]
         return cls + ("(FOO)" if self.kind == 1 else "(FOO,%d)" % self.width)
 
     def write(self, basename, underlying):

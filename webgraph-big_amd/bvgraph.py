@@ -1649,7 +1649,9 @@ class BitStreamArcLabelledImmutableGraph:
         return self.g.outdegree(x)
 
     def decode_range(self, frm, to):
-        """(outdeg, successors, labels) of nodes [frm,to): one batch of the labelled node iterator (:565-582)."""
+        """(outdeg, successors, labels) of nodes [frm,to): one batch of the labelled node iterator (:565-582).
+        EOFException if the label stream does not fit the graph's outdegrees, and if a gamma-coded label is 2^31 or more: the
+        reference's readGamma() would wrap such a value to a negative int; it is refused here (include/bvgraph_hip.h)."""
         deg, succ = self.g.decode_range(frm, to)
         lab = np.empty(max(len(succ), 1), dtype=np.int32)
         n = C.c_uint64()
@@ -1658,7 +1660,8 @@ class BitStreamArcLabelledImmutableGraph:
         return deg, succ, lab[:len(succ)]
 
     def decode_range_lists(self, frm, to):
-        """List labels (FixedWidthIntListLabel: int32 values; FixedWidthLongListLabel: int64): (outdeg, successors, list_off[arcs+1], values)."""
+        """List labels (FixedWidthIntListLabel: int32 values; FixedWidthLongListLabel: int64): (outdeg, successors, list_off[arcs+1], values).
+        EOFException as for decode_range; a gamma-coded list length of 2^31 or more is refused in the same way."""
         deg, succ = self.g.decode_range(frm, to)
         d32 = np.ascontiguousarray(deg, dtype=np.int32)
         loff = np.zeros(len(succ) + 1, dtype=np.uint64)
