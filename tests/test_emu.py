@@ -199,6 +199,67 @@ def test_arc_labels_of_wrong_streams_under_address_sanitizer():
                               LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1")
 
 
+# what of tests/test_gpu_batch.py each lane order runs here (the GPU run has all of it); the forward order in two parts, for the time limit of one run
+BATCH_ON_THE_EMULATOR = {
+    "fwd": "not deep_and_ordinary and not frontier_route and not (prefix_sum and (655 or 70000)) and not (parameter_space and not copies)",
+    "fwd-deep": "deep_and_ordinary",
+    "rev": "reach_boundary or (deep_and_ordinary and not 1500) or (prefix_sum and not 655 and not 70000)",
+}
+
+
+@pytest.mark.parametrize("part", sorted(BATCH_ON_THE_EMULATOR))
+def test_random_access_suite_on_the_emulator(emu_lib, part):
+    """tests/test_gpu_batch.py -- bvg_successors_batch against the adjacency the test wrote down, list for list -- on the CPU.  The forward
+    order runs everything that fits: the reach boundary, deep and ordinary requests together (a part of its own), the capacity contract and
+    the workspace growth and the streams that are wrong IN FULL (items 1, 2, 5 and 9: this is where they are seen first), every tier in one
+    batch, the handles, the wide windows.  The reversed order runs the reach boundary, the deep batches up to 257 requests and the batch
+    sizes up to 4 096: the prefix sum and the row kernel's cross-lane traffic are what the order can break.  Cut from the emulated
+    selection, for time only (all of it runs on the GPU): the batches of 65 535, 65 536, 65 537 and 70 000 requests (96 - 100 s each
+    here; the levels of the prefix sum are crossed here at 1 023 .. 4 096 requests, its serial level's second pass only on the GPU), the
+    parameter sets of the shapes other than "copies" (43 x 2 - 5 s), and the visit on the frontier route (the emulated library is built
+    without bvg_bfs).  The deep batches of 1 500 requests are the dearest thing kept: they belong to item 2, which runs here whole.
+    Measured on one machine, next to the figures of test_arc_label_suite_on_the_emulator: the deep batches of 1 500 requests 204 s (some
+    4 600 requests decoded one by one), the other deep batches 130 s, the reach boundary 36 s, the workspace growth 27 s, the tiers 20 s;
+    the two forward parts together 1 030 s with the batch of 65 537 requests (96 s, cut since: about 930 s), the reversed order 226 s, the
+    randomised test below 103 s + 11 s."""
+    _gpu_file_on_the_emulator(emu_lib, part.split("-")[0], [os.path.join(ROOT, "tests", "test_gpu_batch.py"), "-k", BATCH_ON_THE_EMULATOR[part]])
+
+
+@pytest.mark.parametrize("order,first", [("fwd", 0), ("rev", 11)])
+def test_randomised_random_access_on_the_emulator(emu_lib, order, first):
+    """tests/test_gpu_batch_fuzz.py, ten cases per lane order; the two orders run different cases.  A case costs 1 - 20 s here, except the
+    draws of 6 000 nodes with long chains and thousands of requests, whose deep requests are decoded one by one (a minute and more: case 8
+    of this seed 59 s, case 10 -- left out, for time -- over a minute): the seed is one whose other cases are short (116 s for the first ten)."""
+    _gpu_file_on_the_emulator(emu_lib, order, [os.path.join(ROOT, "tests", "test_gpu_batch_fuzz.py")], BVG_BATCH_FUZZ=str(first + 10), BVG_BATCH_FUZZ_FROM=str(first),
+                              BVG_BATCH_FUZZ_SEED="7")
+
+
+@pytest.mark.skipif(not os.environ.get("BVG_EMU_ASAN"), reason="opt-in (BVG_EMU_ASAN=1): the AddressSanitizer build of the emulated library takes ~4 minutes to compile")
+@pytest.mark.parametrize("with_deep", [False, True])
+def test_workspace_growth_replayed_under_address_sanitizer(W, tmp_path, with_deep):
+    """When the successors no longer fit, bvg_successors_batch frees its workspace, takes a larger one and prepares the batch again in it.
+    Without that second preparation the decode reads the plan, the halos and the prefix sums from the block that was freed: the values are
+    usually still there, on the host and on the device, so no comparison sees it -- AddressSanitizer does.  The calls of
+    test_workspace_growth_between_the_two_preparations (tests/test_gpu_batch.py) are written to files and replayed on one fresh handle by
+    tests/emu/batch_replay.cpp: a program of its own, linked against the sanitizer build of the emulated library, with nothing preloaded."""
+    import numpy as np
+    import batch_cases as BC
+    import test_gpu_batch as TB
+    subprocess.check_call(["make", "-s", "-j4", "-C", EMU, "replay_asan"])
+    h = TB.Hand(W, 7)
+    (tmp_path / "params.bin").write_bytes(bytes(h.st.params))
+    (tmp_path / "graph.bin").write_bytes(h.st.graph.tobytes())
+    (tmp_path / "offsets.bin").write_bytes(h.st.offsets.tobytes())
+    calls = TB.growth_calls(h, with_deep)
+    for name, nodes in calls:
+        deg, succ = BC.expected(h.st.lists, nodes)
+        for ext, a, t in ((".nodes", nodes, "int64"), (".deg", deg, "int32"), (".succ", succ, "int64")):
+            (tmp_path / (name + ext)).write_bytes(np.asarray(a, dtype=t).tobytes())
+    e = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1")
+    out = subprocess.run([os.path.join(EMU, "build", "batch_replay_asan"), str(tmp_path)] + [name for name, _ in calls], env=e, capture_output=True, text=True, timeout=1500)
+    assert out.returncode == 0 and "replay ok" in out.stdout and "ERROR: AddressSanitizer" not in out.stderr, out.stdout[-2000:] + out.stderr[-6000:]
+
+
 def test_randomised_parity_of_the_lean_kernels_on_the_emulator(emu_lib):
     """tests/emu/fuzz_flat.py: random shapes, windows, reference-chain depths, interval lengths, zeta k, LDS geometries (small pools: sub-rows and compaction), records per
     super-row and lane orders; scan_kernel and the experimental flat kernel against the oracle (8 cases here; 90 ran on the final round-5 tree: BVG_EMU_FUZZ=<n> for more)."""
