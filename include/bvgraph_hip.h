@@ -274,6 +274,42 @@ int bvg_geometric(bvg_graph* g, int kind, double param, const double* table, uin
 int bvg_geometric_dev(bvg_graph* g, int kind, double param, const double* table, uint64_t table_len, int64_t from, int64_t to,
                       void* d_centrality, void* d_reachable, uint64_t* hist, uint64_t hist_cap, uint64_t* hist_len, uint64_t* counters);
 
+/* ---- graph statistics (Stats.java) ----
+ * One pass over all successor lists, as Stats.run: arcs, loops, dangling nodes (outdegree 0), terminal nodes (outdegree 0, or one arc that
+ * is a loop), the outdegree and indegree extremes with their nodes, num_gaps / tot_gap (per list of d > 1 arcs: d gaps, (last - first) +
+ * int2nat(first - x)), tot_loc (sum of |y - x| over the arcs) and log_delta[b] = the arcs (x, y), y != x, with msb(|y - x|) == b.  tot_gap
+ * and tot_loc are 128-bit values in two words each.  Ties are the reference's: the smallest node among those of min / max outdegree, the
+ * largest node among those of min / max indegree.  Every integer is exact.  An empty graph gives 0 everywhere except min_outdegree =
+ * min_indegree = INT64_MAX, and distributions of length 1 holding 0.
+ * bvg_stats_compute runs the whole pass and returns an object that holds the summary, both distributions (host memory) and, with
+ * BVG_STATS_KEEP_INDEGREES, the indegree of every node on the device (without it that array is freed once its distribution exists).
+ * Device memory: 4 bytes per node (8 on the 64-bit path) for the indegrees, 4 per node more while the outdegrees are counted, one
+ * arc-bounded batch of the decode (as bvg_components), and 8 bytes per entry of a distribution; BVG_E_NOMEM leaves g usable.  An outdegree
+ * or indegree above 2^31 - 1: BVG_E_UNSUPPORTED (the reference throws).  Malformed streams report the decode's status (a successor
+ * outside [0, nodes): BVG_E_EOF, never used as an index).  g or out NULL, unknown flag bits, node_base != 0: BVG_E_ARG, checked before
+ * any device call.  *out is set to NULL before the pass and stays NULL on every failure of it (BVG_E_EOF, BVG_E_NOMEM, ...): there is
+ * nothing to close then.  The object does not refer to g afterwards.
+ * bvg_stats_distribution: which = BVG_STATS_OUT / BVG_STATS_IN; *len = the largest degree + 1, always written; out[d] = the nodes of
+ * degree d; cap below *len: BVG_E_CAPACITY and out untouched.  bvg_stats_indegrees: the indegrees of [from, to) as int64 (BVG_E_ARG for a
+ * range outside [0, nodes], BVG_E_UNSUPPORTED without BVG_STATS_KEEP_INDEGREES); _dev: into device memory. */
+typedef struct bvg_stats bvg_stats;
+typedef struct bvg_stats_summary {          /* 82 x 8 = 656 bytes */
+    uint64_t nodes, arcs, loops, dangling, terminal, num_gaps;
+    uint64_t tot_gap_lo, tot_gap_hi, tot_loc_lo, tot_loc_hi;
+    int64_t  min_outdegree, max_outdegree, min_outdegree_node, max_outdegree_node;
+    int64_t  min_indegree,  max_indegree,  min_indegree_node,  max_indegree_node;
+    uint64_t log_delta[64];
+} bvg_stats_summary;
+#define BVG_STATS_KEEP_INDEGREES 1u
+#define BVG_STATS_OUT 0
+#define BVG_STATS_IN  1
+int  bvg_stats_compute(bvg_graph* g, uint32_t flags, bvg_stats** out);
+void bvg_stats_close(bvg_stats* s);
+int  bvg_stats_get(const bvg_stats* s, bvg_stats_summary* out);
+int  bvg_stats_distribution(const bvg_stats* s, int which, uint64_t* out, uint64_t cap, uint64_t* len);
+int  bvg_stats_indegrees(bvg_stats* s, int64_t from, int64_t to, int64_t* out);
+int  bvg_stats_indegrees_dev(bvg_stats* s, int64_t from, int64_t to, void* d_out);
+
 /* ---- breadth-first visits (algo/ParallelBreadthFirstVisit.java) ----
  * A visit object keeps on the device what the reference's class keeps (ParallelBreadthFirstVisit.java:79-148): marker[nodes] (-1 = not
  * enqueued yet; otherwise the round in which the node was reached, or its parent with BVG_BFS_PARENT), the round counter (-1 before the

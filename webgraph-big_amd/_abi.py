@@ -89,6 +89,26 @@ def geometric_signatures():
     return {"bvg_geometric": list(args), "bvg_geometric_dev": list(args)}
 
 
+# bvg_stats_compute flags and the `which` of bvg_stats_distribution (BVG_STATS_KEEP_INDEGREES, BVG_STATS_OUT, BVG_STATS_IN)
+STATS_KEEP_INDEGREES_FLAG, STATS_OUT, STATS_IN = 1, 0, 1
+
+
+class StatsSummary(C.Structure):
+    """bvg_stats_summary (82 x 8 = 656 bytes)."""
+    _fields_ = ([(k, C.c_uint64) for k in ("nodes", "arcs", "loops", "dangling", "terminal", "num_gaps", "tot_gap_lo", "tot_gap_hi", "tot_loc_lo", "tot_loc_hi")]
+                + [(k, C.c_int64) for k in ("min_outdegree", "max_outdegree", "min_outdegree_node", "max_outdegree_node",
+                                            "min_indegree", "max_indegree", "min_indegree_node", "max_indegree_node")]
+                + [("log_delta", C.c_uint64 * 64)])
+
+
+def stats_signatures():
+    """argtypes of the bvg_stats_* entry points (graph statistics), by name."""
+    vp, i64, u64, pp = C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(C.c_void_p)
+    return {"bvg_stats_compute": [vp, C.c_uint32, pp], "bvg_stats_close": [vp], "bvg_stats_get": [vp, C.POINTER(StatsSummary)],
+            "bvg_stats_distribution": [vp, C.c_int, vp, u64, C.POINTER(u64)], "bvg_stats_indegrees": [vp, i64, i64, vp],
+            "bvg_stats_indegrees_dev": [vp, i64, i64, vp]}
+
+
 OK, E_ARG, E_STATE, E_UNSUPPORTED, E_IO, E_EOF, E_NOMEM, E_HIP, E_CAPACITY = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 

@@ -208,6 +208,20 @@ def _geometric_fns():
     return L
 
 
+def _stats_fns():
+    """The bvg_stats_* entry points, bound on first use (as _components_fns: a build of the library without them still loads)."""
+    L = lib()
+    if getattr(L, "_stats_bound", False):
+        return L
+    for name, args in _abi.stats_signatures().items():
+        if not hasattr(L, name):
+            raise UnsupportedOperationException(_abi.E_UNSUPPORTED, name + " is not in this build of the library")
+        getattr(L, name).argtypes = args
+    L.bvg_stats_close.restype = None
+    L._stats_bound = True
+    return L
+
+
 def _geometric_coeffs(coeffs):
     """(kind, param, table or None) of what linear_geometric_centrality takes: "harmonic", ("power", e), ("exp", b) or an array."""
     if isinstance(coeffs, str):
@@ -903,6 +917,35 @@ class BVGraph:
         _check(st, "strongly_connected_components_dev")
         return int(cnt.value), dict(zip(SCC_COUNTERS, (int(v) for v in ctr)))
 
+    def stats(self, indegrees=False):
+        """Stats.run (Stats.java) on the device (bvg_stats_compute): one sweep of the compressed graph counts arcs, loops, dangling and
+        terminal nodes, the degree extremes (ties as the reference breaks them: the smallest node for outdegrees, the largest for
+        indegrees), the gap and locality sums (exact Python ints) and the binned gap histogram, and gives both degree distributions.
+        indegrees=True also returns the indegree of every node (int64).  Returns a GraphStats."""
+        L = _stats_fns()
+        h = C.c_void_p()
+        _check(L.bvg_stats_compute(self._h, _abi.STATS_KEEP_INDEGREES_FLAG if indegrees else 0, C.byref(h)), "stats")
+        try:
+            sm = _abi.StatsSummary()
+            _check(L.bvg_stats_get(h, C.byref(sm)), "stats_get")
+            dists = []
+            for which in (_abi.STATS_OUT, _abi.STATS_IN):
+                ln = C.c_uint64(0)
+                st = L.bvg_stats_distribution(h, which, None, 0, C.byref(ln))
+                if st != _abi.E_CAPACITY:
+                    _check(st, "stats_distribution")
+                d = np.zeros(int(ln.value), dtype=np.uint64)
+                _check(L.bvg_stats_distribution(h, which, d.ctypes.data, len(d), C.byref(ln)), "stats_distribution")
+                dists.append(d)
+            ind = None
+            if indegrees:
+                n = int(sm.nodes)
+                ind = np.zeros(n, dtype=np.int64)
+                _check(L.bvg_stats_indegrees(h, 0, n, ind.ctypes.data if n else None), "stats_indegrees")
+        finally:
+            L.bvg_stats_close(h)
+        return GraphStats.from_summary(sm, dists[0], dists[1], ind)
+
     def _geometric_range(self, sources):
         n = self.num_nodes()
         lo, hi = (0, n) if sources is None else (int(sources[0]), int(sources[1]))
@@ -1407,15 +1450,21 @@ def store_scc(result, results_basename):
     return paths
 
 
-def load_scc(results_basename, nodes=None):
-    """Reads back what store_scc wrote: (component, sizes or None, buckets or None) -- int64 arrays and one bool per node (nodes: the
-    length of the bucket array; default: that of the component array)."""
-    comp = np.fromfile(results_basename + ".scc", dtype=">i8").astype(np.int64)
+def _load_scc_sizes_buckets(results_basename, nodes):
+    """(sizes or None, buckets or None) of results_basename.sccsizes / .bucketbits as store_scc writes them, each when the file exists."""
     sp, bp = results_basename + ".sccsizes", results_basename + ".bucketbits"
     sizes = np.fromfile(sp, dtype=">i8").astype(np.int64) if os.path.exists(sp) else None
     buckets = None
     if os.path.exists(bp):
-        buckets = np.unpackbits(np.fromfile(bp, dtype=np.uint8), bitorder="little")[:len(comp) if nodes is None else nodes].astype(bool)
+        buckets = np.unpackbits(np.fromfile(bp, dtype=np.uint8), bitorder="little")[:nodes].astype(bool)
+    return sizes, buckets
+
+
+def load_scc(results_basename, nodes=None):
+    """Reads back what store_scc wrote: (component, sizes or None, buckets or None) -- int64 arrays and one bool per node (nodes: the
+    length of the bucket array; default: that of the component array)."""
+    comp = np.fromfile(results_basename + ".scc", dtype=">i8").astype(np.int64)
+    sizes, buckets = _load_scc_sizes_buckets(results_basename, len(comp) if nodes is None else nodes)
     return comp, sizes, buckets
 
 
@@ -1444,6 +1493,163 @@ def scc_main(argv=None):
         g.close()
     store_scc(r, out)
     print("%d components" % r.count)
+    return r
+
+
+def java_double_str(x):
+    """Double.toString(x): the shortest digits that read back as x, in Java's layout -- plain decimal with at least one fractional digit
+    for 10^-3 <= |x| < 10^7, d.dddE<n> otherwise."""
+    from decimal import Decimal
+    x = float(x)
+    if x != x:
+        return "NaN"
+    if x in (float("inf"), float("-inf")):
+        return "Infinity" if x > 0 else "-Infinity"
+    sign = "-" if str(x).startswith("-") else ""
+    a = abs(x)
+    if a == 0:
+        return sign + "0.0"
+    d = Decimal(repr(a))
+    ds = "".join(str(c) for c in d.as_tuple().digits).rstrip("0") or "0"
+    e = d.adjusted()                                                       # a = d.ddd x 10^e
+    if 1e-3 <= a < 1e7:
+        if e >= 0:
+            ds = ds.ljust(e + 1, "0")
+            return sign + ds[:e + 1] + "." + (ds[e + 1:] or "0")
+        return sign + "0." + "0" * (-e - 1) + ds
+    return sign + ds[0] + "." + (ds[1:] or "0") + "E" + str(e)
+
+
+def _big_decimal_div3(num, den):
+    """new BigDecimal(num).divide(BigDecimal.valueOf(den), 3, RoundingMode.HALF_EVEN).toString() for a non-negative num (an int or a
+    float, taken exactly as BigDecimal(double) does) and an int den > 0.  The quotient is formed with 2 400 digits: a tie at scale 3 is
+    a terminating quotient (an exact double has at most ~1 075 digits), so it is exact there, and any other quotient of these operands
+    lies further than 10^-400 from a tie, so cutting it cannot make one."""
+    import decimal
+    with decimal.localcontext() as c:
+        c.prec = 2400
+        return str((decimal.Decimal(num) / decimal.Decimal(den)).quantize(decimal.Decimal("0.001"), rounding=decimal.ROUND_HALF_EVEN))
+
+
+class GraphStats:
+    """What one pass of Stats.run counts (Stats.java:96-240): nodes, arcs, loops, dangling, terminal, num_gaps, tot_gap and tot_loc
+    (Python ints), min / max outdegree and indegree with their nodes, log_delta (64 bins), outdegree_distribution and
+    indegree_distribution (uint64 arrays of max degree + 1 entries) and, when asked for, indegrees (int64 per node; else None)."""
+
+    FIELDS = ("nodes", "arcs", "loops", "dangling", "terminal", "num_gaps", "tot_gap", "tot_loc", "min_outdegree", "max_outdegree", "min_outdegree_node",
+              "max_outdegree_node", "min_indegree", "max_indegree", "min_indegree_node", "max_indegree_node")
+
+    def __init__(self, log_delta=None, outdegree_distribution=None, indegree_distribution=None, indegrees=None, **fields):
+        unknown = set(fields) - set(self.FIELDS)
+        if unknown:
+            raise TypeError("unknown fields: %s" % sorted(unknown))
+        for k in self.FIELDS:
+            setattr(self, k, int(fields.get(k, (1 << 63) - 1 if k in ("min_outdegree", "min_indegree") else 0)))
+        self.log_delta = [int(v) for v in (log_delta if log_delta is not None else [0] * 64)]
+        self.log_delta += [0] * (64 - len(self.log_delta))
+        self.outdegree_distribution = np.asarray(outdegree_distribution if outdegree_distribution is not None else [0], dtype=np.uint64)
+        self.indegree_distribution = np.asarray(indegree_distribution if indegree_distribution is not None else [0], dtype=np.uint64)
+        self.indegrees = indegrees
+
+    @classmethod
+    def from_summary(cls, sm, outdist, indist, indegrees=None):
+        f = {k: int(getattr(sm, k)) for k in cls.FIELDS if k not in ("tot_gap", "tot_loc")}
+        f["tot_gap"] = (int(sm.tot_gap_hi) << 64) | int(sm.tot_gap_lo)
+        f["tot_loc"] = (int(sm.tot_loc_hi) << 64) | int(sm.tot_loc_lo)
+        return cls([int(v) for v in sm.log_delta], outdist, indist, indegrees, **f)
+
+    def __repr__(self):
+        return "GraphStats(nodes=%d, arcs=%d, loops=%d, dangling=%d)" % (self.nodes, self.arcs, self.loops, self.dangling)
+
+    def properties(self, buckets=None, scc_sizes=None):
+        """The text of resultsBasename.stats: the reference's keys in its order (Stats.java:173-257).  buckets: the number of nodes in
+        buckets, or one bool per node; scc_sizes: the size of every strongly connected component."""
+        import math
+        n = self.nodes
+        div = lambda a, b: a / b if b else float("nan")                   # (Java: 0.0 / 0 is NaN)
+        out = ["nodes=%d" % n, "arcs=%d" % self.arcs, "loops=%d" % self.loops,
+               "successoravggap=" + _big_decimal_div3(self.tot_gap, max(1, self.num_gaps)),
+               "avglocality=" + _big_decimal_div3(self.tot_loc, max(1, self.arcs)),
+               "minoutdegree=%d" % self.min_outdegree, "maxoutdegree=%d" % self.max_outdegree,
+               "minoutdegreenode=%d" % self.min_outdegree_node, "maxoutdegreenode=%d" % self.max_outdegree_node,
+               "dangling=%d" % self.dangling, "terminal=%d" % self.terminal,
+               "percdangling=" + java_double_str(div(100.0 * self.dangling, n)), "avgoutdegree=" + java_double_str(div(float(self.arcs), n))]
+        last = max([i for i in range(64) if self.log_delta[i]], default=-1)
+        tot, num, g = 0.0, 0, 1
+        for i in range(last + 1):                                          # in double, in bin order (Stats.java:193-200); Fast.log2 is log(x) / log(2)
+            num += self.log_delta[i]
+            tot += (math.log(g * 2 + g + 1) / 0.6931471805599453 - 1) * self.log_delta[i]
+            g *= 2
+        out.append("successorlogdeltastats=" + ",".join(str(self.log_delta[i]) for i in range(last + 1)))
+        out.append("successoravglogdelta=" + ("0" if num == 0 else _big_decimal_div3(tot, max(1, num * 2))))
+        out += ["minindegree=%d" % self.min_indegree, "maxindegree=%d" % self.max_indegree, "minindegreenode=%d" % self.min_indegree_node,
+                "maxindegreenode=%d" % self.max_indegree_node, "avgindegree=" + java_double_str(div(float(self.arcs), n))]
+        if buckets is not None:
+            nb = int(buckets) if np.ndim(buckets) == 0 else int(np.count_nonzero(buckets))
+            out += ["buckets=%d" % nb, "percbuckets=" + java_double_str(div(100.0 * nb, n))]
+        if scc_sizes is not None and len(scc_sizes):
+            sz = np.sort(np.asarray(scc_sizes, dtype=np.int64))
+            out += ["sccs=%d" % len(sz), "maxsccsize=%d" % sz[-1], "percmaxscc=" + java_double_str(div(100.0 * int(sz[-1]), n)),
+                    "minsccsize=%d" % sz[0], "percminscc=" + java_double_str(div(100.0 * int(sz[0]), n))]
+        return "".join(l + "\n" for l in out)
+
+
+def _store_longs(values, path):
+    """TextIO.storeLongs: one decimal per line."""
+    with open(path, "w") as f:
+        f.write("".join("%d\n" % int(v) for v in values))
+    return path
+
+
+def store_stats(stats, results_basename, buckets=None, scc_sizes=None, save_degrees=False, outdegrees=None):
+    """Stats.run's output files: results_basename.stats (GraphStats.properties), .outdegree and .indegree (the distributions, one decimal
+    per line, max degree + 1 lines), with scc_sizes .sccdistr (lines size<TAB>count, sizes descending, Stats.java:259-274) and with
+    save_degrees .outdegrees (from `outdegrees`) and .indegrees (from stats.indegrees), one decimal per node.  Returns the paths."""
+    paths = [results_basename + ".stats"]
+    with open(paths[0], "w") as f:
+        f.write(stats.properties(buckets=buckets, scc_sizes=scc_sizes))
+    paths.append(_store_longs(stats.outdegree_distribution, results_basename + ".outdegree"))
+    paths.append(_store_longs(stats.indegree_distribution, results_basename + ".indegree"))
+    if scc_sizes is not None and len(scc_sizes):
+        size, count = np.unique(np.asarray(scc_sizes, dtype=np.int64), return_counts=True)
+        paths.append(results_basename + ".sccdistr")
+        with open(paths[-1], "w") as f:
+            f.write("".join("%d\t%d\n" % (int(s), int(c)) for s, c in zip(size[::-1], count[::-1])))
+    if save_degrees:
+        if outdegrees is None or stats.indegrees is None:
+            raise IllegalArgumentException(_abi.E_ARG, "save_degrees needs the outdegrees and a GraphStats computed with indegrees=True")
+        paths.append(_store_longs(outdegrees, results_basename + ".outdegrees"))
+        paths.append(_store_longs(stats.indegrees, results_basename + ".indegrees"))
+    return paths
+
+
+def stats_arg_parser():
+    """The command line of Stats.main: [-s] basename [resultsBasename]."""
+    import argparse
+    ap = argparse.ArgumentParser(prog="stats", description="Statistical data of a BVGraph, computed on the device: basename.stats, .outdegree, .indegree and, "
+                                 "when basename.sccsizes exists, .sccdistr.  Buckets are read from basename.bucketbits (as the scc tool writes them): the "
+                                 "reference's basename.buckets is a Java-serialised bit vector, which cannot be parsed here and is ignored.")
+    ap.add_argument("-s", "--save-degrees", action="store_true", help="save indegrees and outdegrees in text format (resultsBasename.indegrees, .outdegrees)")
+    ap.add_argument("--device", type=int, default=0, help="the GPU to run on")
+    ap.add_argument("basename", help="the basename of the graph")
+    ap.add_argument("results_basename", nargs="?", default=None, help="the basename of the result files (default: the graph's basename)")
+    return ap
+
+
+def stats_main(argv=None):
+    """Stats.main: loads basename, makes the pass, writes the files of store_stats; basename.sccsizes and basename.bucketbits are used when
+    they exist.  Returns the GraphStats."""
+    args = stats_arg_parser().parse_args(argv)
+    out = args.results_basename or args.basename
+    g = BVGraph.load(args.basename, device=args.device)
+    try:
+        r = g.stats(indegrees=args.save_degrees)
+        outdeg = g.outdegrees() if args.save_degrees else None
+        n = g.num_nodes()
+    finally:
+        g.close()
+    sizes, buckets = _load_scc_sizes_buckets(args.basename, n)                 # (load_scc's reader; the .scc labels themselves are not needed)
+    store_stats(r, out, buckets=buckets, scc_sizes=sizes, save_degrees=args.save_degrees, outdegrees=outdeg)
     return r
 
 

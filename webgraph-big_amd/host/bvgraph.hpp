@@ -180,6 +180,8 @@ public:
     }
     // strongly connected components (algo/StronglyConnectedComponents.java) on the device: the class is below
     inline class StronglyConnectedComponents stronglyConnectedComponents(bool computeBuckets = false);
+    // graph statistics on the device (Stats.java): the class is below
+    inline class GraphStats stats(bool keepIndegrees = false);
     // exact geometric centralities on the device (algo/LinearGeometricCentrality.java): the class and the coefficient objects are below
     template <typename Coeffs> inline class LinearGeometricCentrality linearGeometricCentrality(const Coeffs& coeffs);
     // breadth-first visits on the device (algo/ParallelBreadthFirstVisit.java): the class is below
@@ -237,6 +239,41 @@ public:
     }
 };
 inline StronglyConnectedComponents BVGraph::stronglyConnectedComponents(bool computeBuckets) { return StronglyConnectedComponents(shared_from_this(), computeBuckets); }
+
+// GraphStats (Stats.java) over bvg_stats_*: what one pass of Stats.run counts -- the summary (arcs, loops, dangling and terminal nodes, the
+// degree extremes with the reference's tie rules, the gap and locality sums as 128-bit values in two words, the binned gap histogram),
+// both degree distributions and, with keepIndegrees, the indegree of every node (kept on the device, copied on request).
+class GraphStats {
+    bvg_stats* s_ = nullptr;
+    std::vector<uint64_t> distribution(int which) const {
+        uint64_t len = 0;
+        int st = bvg_stats_distribution(s_, which, nullptr, 0, &len);
+        if (st != BVG_E_CAPACITY) check(st, "stats_distribution");
+        std::vector<uint64_t> out((size_t)len);
+        check(bvg_stats_distribution(s_, which, out.data(), len, &len), "stats_distribution");
+        return out;
+    }
+public:
+    bvg_stats_summary summary{};
+    GraphStats(BVGraph& g, bool keepIndegrees);
+    ~GraphStats() { if (s_) bvg_stats_close(s_); }
+    GraphStats(const GraphStats&) = delete; GraphStats& operator=(const GraphStats&) = delete;
+    GraphStats(GraphStats&& o) noexcept : s_(o.s_), summary(o.summary) { o.s_ = nullptr; }
+    std::vector<uint64_t> outdegreeDistribution() const { return distribution(BVG_STATS_OUT); }
+    std::vector<uint64_t> indegreeDistribution() const { return distribution(BVG_STATS_IN); }
+    // the indegrees of [from, to) (to < 0: up to the last node); needs keepIndegrees
+    std::vector<int64_t> indegrees(int64_t from = 0, int64_t to = -1) {
+        if (to < 0) to = (int64_t)summary.nodes;
+        std::vector<int64_t> out(to > from ? (size_t)(to - from) : 0);
+        check(bvg_stats_indegrees(s_, from, to, out.empty() ? nullptr : out.data()), "stats_indegrees");
+        return out;
+    }
+};
+inline GraphStats::GraphStats(BVGraph& g, bool keepIndegrees) {
+    check(bvg_stats_compute(g.handle(), keepIndegrees ? BVG_STATS_KEEP_INDEGREES : 0u, &s_), "stats_compute");
+    check(bvg_stats_get(s_, &summary), "stats_get");
+}
+inline GraphStats BVGraph::stats(bool keepIndegrees) { return GraphStats(*this, keepIndegrees); }
 
 // The coefficient objects of LinearGeometricCentrality (LinearGeometricCentrality.java:82-124): get(d) is what the library evaluates.
 struct HarmonicCoefficients { double get(int64_t d) const { return d == 0 ? 0.0 : 1.0 / (double)d; } };
