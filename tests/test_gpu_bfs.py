@@ -410,6 +410,22 @@ def test_empty_runs_under_tiny_budgets(W, tools, monkeypatch, budget):
     check_visit(g, off, adj, sweep_cases.NODES - 1, both_modes=False)          # from a node without successors
 
 
+# lists and groups of 64 lists that end on, just past and across the edges of the mark kernel's chunks of 64 arcs (sweep route, both modes)
+@pytest.mark.parametrize("budget", [None, "61"])
+def test_chunk_edges_under_budgets(W, tools, monkeypatch, budget):
+    monkeypatch.setenv("BVG_BFS_ROUTE", "sweep")
+    if budget is None:
+        monkeypatch.delenv("BVG_BFS_BATCH_ARCS", raising=False)
+    else:
+        monkeypatch.setenv("BVG_BFS_BATCH_ARCS", budget)
+    off, adj = sweep_cases.chunk_edges_graph()
+    g = open_graph(W, tools, off, adj)
+    for start in (0, 128):                                                     # level 1 expands every other list at once; from 128: node 0 alone
+        queue, _, dist, _, c = check_visit(g, off, adj, start)
+        assert len(queue) == sweep_cases.CHUNK_NODES and c["frontier_levels"] == 0 and c["sweep_levels"] >= 3
+        assert all(dist[x] <= 2 for x in sweep_cases.CHUNK_LISTS)
+
+
 @pytest.mark.parametrize("depth", [1, 5, 12])
 def test_complete_binary_trees(W, tools, depth):
     n = (1 << (depth + 1)) - 1

@@ -195,6 +195,20 @@ def test_empty_runs_under_tiny_budgets(W, tools, monkeypatch, budget):
     check(g, len(off) - 1, *arcs_of(off, adj))
 
 
+# 4c. lists and groups of 64 lists that end on, just past and across the edges of the hook kernel's chunks of 64 arcs
+@pytest.mark.parametrize("budget", [None, "61"])
+def test_chunk_edges_under_budgets(W, tools, monkeypatch, budget):
+    if budget is None:
+        monkeypatch.delenv("BVG_CC_BATCH_ARCS", raising=False)
+    else:
+        monkeypatch.setenv("BVG_CC_BATCH_ARCS", budget)
+    off, adj = sweep_cases.chunk_edges_graph()
+    st = tools.store((off, adj), threads=2)
+    g = W.BVGraph.from_memory(st.params, st.graph, st.offsets)
+    k, _, sizes = check(g, len(off) - 1, *arcs_of(off, adj))
+    assert k == 1 and sizes[0] == sweep_cases.CHUNK_NODES                      # every node is a successor of a node with a list
+
+
 # 5. sortBySize and a sizes buffer that is too small
 def test_sort_by_size_and_capacity(W, tools):
     n = 20000

@@ -153,6 +153,23 @@ def test_empty_runs_under_tiny_budgets(W, tools, monkeypatch, budget):
         assert r.counters["words_per_node"] == 2 and r.counters["passes"] == 1 and r.counters["batch_decodes"] > r.counters["sweeps"]
 
 
+# 4b. lists and groups of 64 lists that end on, just past and across the edges of the mark kernel's chunks of 64 arcs
+@pytest.mark.parametrize("budget", [None, "61"])
+def test_chunk_edges_under_budgets(W, tools, monkeypatch, budget):
+    if budget is None:
+        monkeypatch.delenv("BVG_GEO_BATCH_ARCS", raising=False)
+    else:
+        monkeypatch.setenv("BVG_GEO_BATCH_ARCS", budget)
+    off, adj = sweep_cases.chunk_edges_graph()
+    counts = M.distance_counts(off, adj, range(sweep_cases.CHUNK_NODES))
+    assert all(M.reachable(counts)[x] == sweep_cases.CHUNK_NODES for x in sweep_cases.CHUNK_LISTS)
+    g = graph_of(W, tools, off, adj)
+    for spec in ("harmonic", [0, 1, 1]):
+        r = check(g, counts, spec)
+        assert r.counters["single_resident_batch"] == (1 if budget is None else 0)
+        assert r.counters["batch_decodes"] == 1 if budget is None else r.counters["batch_decodes"] > r.counters["sweeps"]
+
+
 # 5. the golden graph
 @pytest.fixture(scope="module")
 def cnr_counts(cnr_csr):

@@ -172,6 +172,24 @@ def test_empty_runs_under_tiny_budgets(W, tools, monkeypatch, budget):
     assert r.counters["batch_decodes"] > r.counters["sweeps"]
 
 
+# 5b. lists and groups of 64 lists that end on, just past and across the edges of the sweep kernel's chunks of 64 arcs
+@pytest.mark.parametrize("budget", [None, "61"])
+def test_chunk_edges_under_budgets(W, tools, monkeypatch, budget):
+    if budget is None:
+        monkeypatch.delenv("BVG_SCC_BATCH_ARCS", raising=False)
+    else:
+        monkeypatch.setenv("BVG_SCC_BATCH_ARCS", budget)
+    off, adj = sweep_cases.chunk_edges_graph()
+    n = len(off) - 1
+    src, dst = arcs_of(off, adj)
+    expect = cpu_scc(n, src, dst)
+    assert expect[0] == n - len(sweep_cases.CHUNK_LISTS) + 1 and expect[2].max() == len(sweep_cases.CHUNK_LISTS)   # the nodes with a list are one SCC
+    g = graph_of(W, tools, off, adj)
+    r = check(g, n, src, dst, expect=expect)
+    assert r.counters["single_resident_batch"] == (1 if budget is None else 0)
+    assert r.counters["batch_decodes"] == 1 if budget is None else r.counters["batch_decodes"] > r.counters["sweeps"]
+
+
 # 6. neither the pivot nor the scheduling reaches the result
 def test_result_does_not_depend_on_the_pivot(W, tools, monkeypatch):
     n = 20000

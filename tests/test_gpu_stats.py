@@ -64,6 +64,18 @@ def test_empty_runs_under_every_budget(W, tools, monkeypatch, budget):
     assert zeros - 600 == int(np.count_nonzero(deg[200:400] == 0) + np.count_nonzero(deg[600:800] == 0))
 
 
+# 2b. lists and groups of 64 lists that end on, just past and across the edges of the sweep kernel's chunks of 64 arcs
+@pytest.mark.parametrize("budget", [None, "61"])
+def test_chunk_edges_under_budgets(W, tools, monkeypatch, budget):
+    if budget is None:
+        monkeypatch.delenv("BVG_STATS_BATCH_ARCS", raising=False)
+    else:
+        monkeypatch.setenv("BVG_STATS_BATCH_ARCS", budget)
+    off, adj = sweep_cases.chunk_edges_graph()
+    _, m = check(W, tools, off, adj)
+    assert m["dangling"] == sweep_cases.CHUNK_NODES - len(sweep_cases.CHUNK_LISTS)
+
+
 # 3. sizes around a wavefront and a workgroup
 @pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 255, 256, 257, 1025])
 def test_sizes_around_a_wavefront_and_a_workgroup(W, tools, n):

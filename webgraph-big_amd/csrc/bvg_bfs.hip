@@ -12,7 +12,7 @@
 //                          mark kernel takes the lists whose source has dist == d.  Random access to a large share of the graph costs more than
 //                          decoding all of it in order.
 //   mark       one wavefront per 64 lists: the lengths of the lists to expand are prefix-summed across the wavefront (LDS), then the lanes walk
-//              those arcs in chunks of 64 -- the owner of arc t is found by binary search over the list ends, as in cc_hook_kernel.  Per arc: bounds
+//              those arcs in chunks of 64 -- the owner of arc t is found by binary search over the list ends (bvg_arcwalk.h).  Per arc: bounds
 //              check, a plain load of marker[y], and only for an unmarked y an atomic.  The lane that wins y sets dist[y] = d + 1 and appends y to
 //              a short list (one atomic per wavefront and chunk).
 //   next       the next level in increasing id, without a sort of the graph's size: when the winners fit the short list it is radix-sorted into the
@@ -40,14 +40,13 @@
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
+#include "bvg_arcwalk.h"
 #include "bvg_host.h"
 #include "../../include/bvgraph_hip.h"
 
 namespace bvg {
 
 namespace {
-
-template <typename T> __device__ __forceinline__ constexpr T none() { return (T)~(T)0; }   // the marker's -1 (never a node: the 32-bit kernels stop at 2^32 - 256 nodes)
 
 enum : int { kCtlBad = 0, kCtlCount = 1, kCtlFirst = 2, kCtlWords = 4 };   // control words (unsigned long long) the host reads back
 
@@ -64,15 +63,15 @@ template <typename T> __global__ void bfs_seed_kernel(int64_t start, T mark, T* 
 }
 
 // One wavefront per 64 consecutive lists of the batch (four per workgroup): list i holds succ[cum[i] .. cum[i + 1]) and belongs to node
-// nodes[i] (frontier route: every list is expanded) or lo + i (SWEEP: only when dist[lo + i] == d).
+// nodes[i] (frontier route: every list is expanded) or lo + i (SWEEP: only when dist[lo + i] == d).  The arcs of the lists to expand are
+// walked as bvg_arcwalk.h describes.  none<T>() (there too) is the marker's -1.
 template <typename T, bool PARENT, bool SWEEP>
 __global__ void __launch_bounds__(256) bfs_mark_kernel(const uint64_t* cum, const int64_t* nodes, int64_t lo, int64_t cnt, const int64_t* succ, int64_t n, T* marker, T* cand,
                                                        int32_t* dist, int32_t d, T round, unsigned long long* ctl, int64_t* small, uint64_t small_cap) {
-    __shared__ uint64_t vend_s[4][64];     // inclusive prefix sums of the lengths of the lists to expand ("virtual" arc indices)
-    __shared__ uint64_t base_s[4][64];     // real index of virtual arc t of list l = base[l] + t (mod 2^64)
+    __shared__ ArcWalk walk_s[4];
     __shared__ T src_s[4][64];
     const unsigned w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint64_t* vend = vend_s[w]; uint64_t* base = base_s[w]; T* src = src_s[w];
+    ArcWalk& walk = walk_s[w]; T* src = src_s[w];
     bool oob = false;
     for (int64_t x0 = ((int64_t)blockIdx.x * 4 + w) * 64; x0 < cnt; x0 += (int64_t)gridDim.x * 256) {   // (whole wavefronts: no workgroup barrier)
         const int64_t i = x0 + lane;
@@ -80,20 +79,12 @@ __global__ void __launch_bounds__(256) bfs_mark_kernel(const uint64_t* cum, cons
         const uint64_t b = valid ? cum[i] : 0, e = valid ? cum[i + 1] : 0;
         const int64_t u = valid ? (SWEEP ? lo + i : nodes[i]) : 0;
         const bool act = valid && e > b && (!SWEEP || dist[u] == d);
-        const uint64_t len = act ? e - b : 0;
-        uint64_t inc = len;
-        for (unsigned o = 1; o < 64; o <<= 1) { const uint64_t t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-        const uint64_t total = __shfl(inc, 63, 64);
+        const uint64_t total = walk.begin(lane, act, b, e, [&] { src[lane] = (T)u; });
         if (total == 0) continue;                                            // (uniform: nothing of this group is in the level)
-        vend[lane] = inc; base[lane] = b - (inc - len); src[lane] = (T)u;
-        __builtin_amdgcn_wave_barrier();                                     // (LDS operations of one wavefront complete in order)
-        for (uint64_t t0 = 0; t0 < total; t0 += 64) {                        // (uniform trip count: ballots below)
-            const uint64_t t = t0 + lane;
+        walk.for_each_chunk(lane, total, [&](bool has, int l, uint64_t at) {  // (the uniform walk: ballots below)
             bool won = false; int64_t y = 0;
-            if (t < total) {
-                int l = 0, r = 63;                                           // first list whose end is > t (vend[63] = total > t)
-                while (l < r) { const int m = (l + r) >> 1; if (vend[m] <= t) l = m + 1; else r = m; }
-                y = succ[base[l] + t];
+            if (has) {
+                y = succ[at];
                 if (y < 0 || y >= n) oob = true;                             // malformed stream: flagged, never used as an index
                 else if (marker[y] == none<T>()) {
                     if (PARENT) {
@@ -109,13 +100,13 @@ __global__ void __launch_bounds__(256) bfs_mark_kernel(const uint64_t* cum, cons
             const uint64_t wins = __ballot(won);
             if (wins) {                                                      // one atomic per wavefront and chunk
                 const unsigned leader = (unsigned)__builtin_ctzll(wins);
-                unsigned long long at = 0;
-                if (lane == leader) at = atomicAdd(ctl + kCtlCount, (unsigned long long)__builtin_popcountll(wins));
-                at = __shfl(at, (int)leader, 64) + (unsigned long long)__builtin_popcountll(wins & ((1ull << lane) - 1));
-                if (won && at < small_cap) small[at] = y;
+                unsigned long long at_q = 0;
+                if (lane == leader) at_q = atomicAdd(ctl + kCtlCount, (unsigned long long)__builtin_popcountll(wins));
+                at_q = __shfl(at_q, (int)leader, 64) + (unsigned long long)__builtin_popcountll(wins & ((1ull << lane) - 1));
+                if (won && at_q < small_cap) small[at_q] = y;
             }
-        }
-        __builtin_amdgcn_wave_barrier();                                     // (the next group's LDS writes after every lane's reads)
+        });
+        walk.end();
     }
     if (oob) atomicOr(ctl + kCtlBad, 1ull);
 }

@@ -27,6 +27,7 @@
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "bvg_arcwalk.h"
 #include "bvg_host.h"
 #include "../../include/bvgraph_hip.h"
 
@@ -69,40 +70,34 @@ template <typename T> __global__ void cc_init_kernel(T* parent, int64_t n) {
     BVG_FOR(x, n) parent[x] = (T)x;
 }
 
-// One wavefront per 64 consecutive nodes of the batch [lo, lo + cnt) (four per workgroup): the root of every source is found once per
-// list (LDS), then the lanes walk the 64 lists' arcs in chunks of 64 -- the owner of arc t is the number of list ends <= t, as in
-// expand_sources_kernel (bvg_transpose.hip) -- find the target's root and unite when the roots differ.  A target outside [0, n) is a
-// malformed stream: it is flagged (*bad) and not followed.
+// One wavefront per 64 consecutive nodes of the batch [lo, lo + cnt) (four per workgroup), its arcs walked as bvg_arcwalk.h describes: the
+// root of every source is found once per list (LDS); per arc, find the target's root and unite when the roots differ.  A target outside
+// [0, n) is a malformed stream: it is flagged (*bad) and not followed.
 template <typename T> __global__ void __launch_bounds__(256) cc_hook_kernel(const uint64_t* cum, int64_t lo, int64_t cnt, const int64_t* succ, int64_t n,
                                                                             T* parent, unsigned* bad) {
-    __shared__ uint64_t ends_s[4][64];
+    __shared__ ArcWalk walk_s[4];
     __shared__ T root_s[4][64];
     const unsigned w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int64_t x0 = ((int64_t)blockIdx.x * 4 + w) * 64; x0 < cnt; x0 += (int64_t)gridDim.x * 256) {   // (whole wavefronts: no workgroup barrier)
-    const int64_t xe = x0 + 64 < cnt ? x0 + 64 : cnt;
-    const int c = (int)(xe - x0);
-    uint64_t* ends = ends_s[w]; T* roots = root_s[w];
-    const uint64_t a0 = cum[x0], a1 = cum[xe];
-    if ((int)lane < c) {
-        const uint64_t e = cum[x0 + lane + 1];
-        ends[lane] = e;
-        roots[lane] = e > cum[x0 + lane] ? find_root(parent, (T)(lo + x0 + lane)) : (T)0;   // (no arcs: never read)
-    }
-    __builtin_amdgcn_wave_barrier();                                    // (LDS operations of one wavefront complete in order)
+    ArcWalk& walk = walk_s[w]; T* roots = root_s[w];
     bool oob = false;
-    for (uint64_t t = a0 + lane; t < a1; t += 64) {
-        int l = 0, r = c;
-        while (l < r) { const int m = (l + r) >> 1; if (ends[m] <= t) l = m + 1; else r = m; }
-        const int64_t y = succ[t];
-        if (y < 0 || y >= n) { oob = true; continue; }
-        const T ru = roots[l];
-        const T pv = ld_parent(parent + y);
-        if (pv == ru) continue;                                         // (the common case once the source's component is hooked: one load)
-        const T rv = find_root_from(parent, (T)y, pv);
-        if (ru != rv) unite(parent, ru, rv);
-    }
-    if (oob) atomicOr(bad, 1u);
-    __builtin_amdgcn_wave_barrier();                                    // (the next group's LDS writes after every lane's reads)
+    for (int64_t x0 = ((int64_t)blockIdx.x * 4 + w) * 64; x0 < cnt; x0 += (int64_t)gridDim.x * 256) {   // (whole wavefronts: no workgroup barrier)
+        const int64_t i = x0 + lane;
+        const bool valid = i < cnt;
+        const uint64_t b = valid ? cum[i] : 0, e = valid ? cum[i + 1] : 0;
+        const bool act = e > b;
+        const uint64_t total = walk.begin(lane, act, b, e, [&] { roots[lane] = act ? find_root(parent, (T)(lo + i)) : (T)0; });   // (no arcs: never read)
+        if (total == 0) continue;                                            // (uniform: no list of this group has an arc)
+        walk.for_each_arc(lane, total, [&](int l, uint64_t at) {
+            const int64_t y = succ[at];
+            if (y < 0 || y >= n) { oob = true; return; }
+            const T ru = roots[l];
+            const T pv = ld_parent(parent + y);
+            if (pv == ru) return;                                            // (the common case once the source's component is hooked: one load)
+            const T rv = find_root_from(parent, (T)y, pv);
+            if (ru != rv) unite(parent, ru, rv);
+        });
+        if (oob) atomicOr(bad, 1u);
+        walk.end();
     }
 }
 

@@ -40,6 +40,7 @@
 #include <cstdint>
 #include <cstring>
 
+#include "bvg_arcwalk.h"
 #include "bvg_host.h"
 #include "../../include/bvgraph_hip.h"
 
@@ -51,18 +52,16 @@ enum : int { kCtlBad, kCtlTotal, kCtlWords };                                // 
 
 template <int W> struct alignas(W >= 2 ? 16 : 8) Words { uint64_t w[W]; };  // the words of one node: one or more 16-byte accesses
 
-// One wavefront per 64 consecutive lists of the batch [lo, lo + cnt) (four per workgroup), as scc_sweep_kernel / bfs_mark_kernel: the lengths
-// of the lists that take part (some word of frontier[x] is non-zero) are prefix-summed across the wavefront, then the lanes walk those arcs
-// in chunks of 64 -- the owner of arc t is found by binary search over the list ends in LDS, where its frontier words are too.  A target
+// One wavefront per 64 consecutive lists of the batch [lo, lo + cnt) (four per workgroup); the arcs of the lists that take part (some word
+// of frontier[x] is non-zero) are walked as bvg_arcwalk.h describes, the lists' frontier words being in LDS next to the list ends.  A target
 // outside [0, n) is a malformed stream: it is flagged and never used as an index.
 template <int W>
 __global__ void __launch_bounds__(256) geo_mark_kernel(const uint64_t* cum, int64_t lo, int64_t cnt, const int64_t* succ, int64_t n, const uint64_t* seen,
                                                        const uint64_t* frontier, uint64_t* next, unsigned long long* ctl) {
-    __shared__ uint64_t vend_s[4][64];     // inclusive prefix sums of the lengths of the lists that take part ("virtual" arc indices)
-    __shared__ uint64_t base_s[4][64];     // real index of virtual arc t of list l = base[l] + t (mod 2^64)
+    __shared__ ArcWalk walk_s[4];
     __shared__ uint64_t fr_s[4][64 * W];   // frontier[x][k] of list l at l * W + k
     const unsigned w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint64_t* vend = vend_s[w]; uint64_t* base = base_s[w]; uint64_t* fr = fr_s[w];
+    ArcWalk& walk = walk_s[w]; uint64_t* fr = fr_s[w];
     bool oob = false;
     for (int64_t x0 = ((int64_t)blockIdx.x * 4 + w) * 64; x0 < cnt; x0 += (int64_t)gridDim.x * 256) {   // (whole wavefronts: no workgroup barrier)
         const int64_t i = x0 + lane;
@@ -75,28 +74,22 @@ __global__ void __launch_bounds__(256) geo_mark_kernel(const uint64_t* cum, int6
 #pragma unroll
             for (int k = 0; k < W; k++) act |= f.w[k] != 0;
         }
-        const uint64_t len = act ? e - b : 0;
-        uint64_t inc = len;
-        for (unsigned o = 1; o < 64; o <<= 1) { const uint64_t t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-        const uint64_t total = __shfl(inc, 63, 64);
-        if (total == 0) continue;                                            // (uniform: no list of this group takes part)
-        vend[lane] = inc; base[lane] = b - (inc - len);
+        const uint64_t total = walk.begin(lane, act, b, e, [&] {
 #pragma unroll
-        for (int k = 0; k < W; k++) fr[lane * W + k] = f.w[k];
-        __builtin_amdgcn_wave_barrier();                                     // (LDS operations of one wavefront complete in order)
-        for (uint64_t t = lane; t < total; t += 64) {
-            int l = 0, r = 63;                                               // first list whose end is > t (vend[63] = total > t)
-            while (l < r) { const int m = (l + r) >> 1; if (vend[m] <= t) l = m + 1; else r = m; }
-            const int64_t y = succ[base[l] + t];
-            if (y < 0 || y >= n) { oob = true; continue; }
+            for (int k = 0; k < W; k++) fr[lane * W + k] = f.w[k];
+        });
+        if (total == 0) continue;                                            // (uniform: no list of this group takes part)
+        walk.for_each_arc(lane, total, [&](int l, uint64_t at) {
+            const int64_t y = succ[at];
+            if (y < 0 || y >= n) { oob = true; return; }
             const Words<W> s = *(const Words<W>*)(seen + y * W);
 #pragma unroll
             for (int k = 0; k < W; k++) {
                 const uint64_t m = fr[l * W + k] & ~s.w[k];
                 if (m && (m & ~next[y * W + k])) (void)__hip_atomic_fetch_or(next + y * W + k, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (a stale next: a needless atomic)
             }
-        }
-        __builtin_amdgcn_wave_barrier();                                     // (the next group's LDS writes after every lane's reads)
+        });
+        walk.end();
     }
     if (oob) atomicOr(ctl + kCtlBad, 1ull);
 }
@@ -226,10 +219,8 @@ template <int W> int geometric_t(bvg_graph* g, const Coefficients& coeff, int64_
     int rc = arc_budget(n, kMaxBatchArcs, "BVG_GEO_BATCH_ARCS", &per); if (rc) return rc;
     bvghost::SweepPlan sp;
     rc = sp.build(g, per); if (rc) return rc;
-    const bool single = sp.batches.size() == 1;
-    bool decoded = false;
     if (!sp.batches.empty()) { if (ws.alloc(sp.bytes)) return BVG_E_NOMEM; sp.bind(ws.p); }
-    counters[kWordsUsed] = W; counters[kResident] = single ? 1 : 0;
+    counters[kWordsUsed] = W; counters[kResident] = sp.single() ? 1 : 0;
     HIPCHK(hipMemsetAsync(ctl, 0, kCtlWords * 8, g->stream));
     std::vector<uint64_t> hist(1, 0);
     const double coeff0 = coeff(0);
@@ -241,7 +232,7 @@ template <int W> int geometric_t(bvg_graph* g, const Coefficients& coeff, int64_
         hipLaunchKernelGGL((geo_seed_kernel<W>), dim3((S + 255) / 256), dim3(256), 0, g->stream, seen, frontier, s0, in_pass, acc, reach, cnt);
         for (uint64_t d = 1;; d++) {
             for (const Batch& b : sp.batches) {
-                if (!(single && decoded)) { rc = sp.decode(g, b); if (rc) return rc; counters[kDecodes]++; decoded = true; }
+                rc = sp.load(g, b, &counters[kDecodes]); if (rc) return rc;
                 const int64_t nb = b.hi - b.lo;
                 hipLaunchKernelGGL((geo_mark_kernel<W>), dim3(grid(nb, 256)), dim3(256), 0, g->stream, (const uint64_t*)sp.cum(), b.lo, nb, (const int64_t*)sp.succ(), n,
                                    (const uint64_t*)seen, (const uint64_t*)frontier, next, ctl);

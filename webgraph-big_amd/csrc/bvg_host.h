@@ -5,6 +5,7 @@
 //   bvg_index.hip   (kernels) + bvg_index_host.hip: the residual skip index -- granularity, the build (counting pass, dense walk, validating pass), basename.bvgidx on disk
 //   bvg_sched.hip   run_decode: the tier scheduler (tier 0 + LDS classes + giants launched side by side, fail-over, what a scan learns about its blocks)
 //   bvg_api.hip     the extern "C" entry points
+//   bvg_arcwalk.h   (not included here: device-only) how the kernels of the analytics walk the arcs of a decoded batch, the device half of that sweep
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -255,7 +256,9 @@ struct Stopwatch {
 
 // ---- bvg_plan.hip: arc-bounded batches.  The graph (or any list of lists with prefix sums on the device) cut into ranges of at most `per` arcs, and
 // the sweep over the whole compressed graph in such ranges that bvg_components, the sweep route of bvg_bfs_visit and bvg_hyperball_iterate
-// share: index_first, arc_budget, then a SweepPlan and per batch SweepPlan::decode followed by the caller's own kernel.  The caller owns the
+// share: index_first, arc_budget, then a SweepPlan and per batch SweepPlan::decode followed by the caller's own kernel (bvg_arcwalk.h: how the
+// kernels that consume a batch arc by arc walk it).  A caller that sweeps many times (bvg_scc, bvg_geometric) calls SweepPlan::load instead: a
+// plan of one batch stays resident in the workspace and is decoded once.  The caller owns the
 // workspace (components: per call, freed before the numbering pass; bfs: grown on demand; hyperball: once per plan) and the order of these
 // steps against its own allocations, which decides how much memory a batch takes on a full card.
 constexpr int64_t kMaxBatchNodes = 1ll << 30;      // node ranges of a launch stay well below 2^32 work-items
@@ -273,11 +276,14 @@ struct SweepPlan {
     char* base = nullptr;
     int build(bvg_graph* g, uint64_t per, bool every_node = false);
     void layout(size_t extra_bytes);
-    void bind(void* ws) { base = (char*)ws; }
+    bool resident = false;                                                           // the plan's one batch is decoded in the bound workspace
+    void bind(void* ws) { base = (char*)ws; resident = false; }
+    bool single() const { return batches.size() == 1; }
     uint64_t* cum() const { return (uint64_t*)base; }
     int64_t* succ() const { return (int64_t*)(base + o_succ); }
     void* extra() const { return base + o_extra; }
     int decode(bvg_graph* g, const Batch& b) const;
+    int load(bvg_graph* g, const Batch& b, uint64_t* decodes);
 };
 
 // ---- bvg_components.hip: the numbering that bvg_components and bvg_scc share.  d_parent (uint32 per node, uint64 when `wide`) holds trees whose roots

@@ -459,5 +459,14 @@ int SweepPlan::decode(bvg_graph* g, const Batch& b) const {
     return run_decode(g, b.lo, b.hi, true, cum(), succ(), nullptr, nullptr);
 }
 
+// decode(b), unless b is the plan's only batch and is in the bound workspace already (nothing else is ever decoded into it: the batch stays
+// resident until the next bind).  *decodes += 1 when a decode ran
+int SweepPlan::load(bvg_graph* g, const Batch& b, uint64_t* decodes) {
+    if (single() && resident) return 0;
+    const int rc = decode(g, b); if (rc) return rc;
+    ++*decodes; resident = single();
+    return 0;
+}
+
 
 }  // namespace bvghost

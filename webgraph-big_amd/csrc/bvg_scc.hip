@@ -43,6 +43,7 @@
 #include <cstdint>
 #include <cstring>
 
+#include "bvg_arcwalk.h"
 #include "bvg_host.h"
 #include "../../include/bvgraph_hip.h"
 
@@ -50,31 +51,29 @@ namespace bvg {
 
 namespace {
 
-template <typename T> __device__ __host__ __forceinline__ constexpr T none() { return (T)~(T)0; }   // rep: live; colour: retired (never a node: the 32-bit kernels stop at 2^32 - 256 nodes)
-
+// none<T>() (bvg_arcwalk.h): rep: live; colour: retired
 enum : int { kTrim, kFw, kBw, kColour, kBucket };                                 // modes of the sweep kernel
 enum : unsigned { fIn = 1, fOut = 2, fFw = 4, fBw = 8, fArc = 1, fLeave = 2 };    // flag bits (the bucket sweep reuses the trim bits, on representatives)
+enum : unsigned { mOob = 1, mWrote = 2 };                                         // what a lane of the sweep kernel met: a target outside [0, n); a write that counts for the fixpoint
 enum : int { kCtlBad, kCtlChanged, kCtlCount, kCtlRoots, kCtlMaxDeg, kCtlPivot, kCtlWords = 8 };   // control words (unsigned long long) the host reads back
 
 __device__ __forceinline__ void set_flag(uint8_t* flags, int64_t x, unsigned bits) {
     __hip_atomic_fetch_or((unsigned*)flags + (x >> 2), bits << (8 * (unsigned)(x & 3)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// One wavefront per 64 consecutive lists of the batch [lo, lo + cnt) (four per workgroup), as bfs_mark_kernel: the lengths of the lists
-// whose source takes part (live; kFw: has fw; kBw: has no bw yet) are prefix-summed across the wavefront, then the lanes walk those arcs in
-// chunks of 64 -- the owner of arc t is found by binary search over the list ends in LDS.  `key` is colour[] (kBucket: rep[]).  What an arc
-// gives its SOURCE (has-live-out, bw, the bucket bits) is collected per list in LDS and written once per list.  A target outside [0, n) is a
+// One wavefront per 64 consecutive lists of the batch [lo, lo + cnt) (four per workgroup); the arcs of the lists whose source takes part
+// (live; kFw: has fw; kBw: has no bw yet) are walked as bvg_arcwalk.h describes.  `key` is colour[] (kBucket: rep[]).  What an arc gives
+// its SOURCE (has-live-out, bw, the bucket bits) is collected per list in LDS and written once per list.  A target outside [0, n) is a
 // malformed stream: it is flagged and never used as an index.
 template <typename T, int MODE>
 __global__ void __launch_bounds__(256) scc_sweep_kernel(const uint64_t* cum, int64_t lo, int64_t cnt, const int64_t* succ, int64_t n, const T* key, T* colour,
                                                         uint8_t* flags, unsigned long long* ctl) {
-    __shared__ uint64_t vend_s[4][64];     // inclusive prefix sums of the lengths of the lists that take part ("virtual" arc indices)
-    __shared__ uint64_t base_s[4][64];     // real index of virtual arc t of list l = base[l] + t (mod 2^64)
+    __shared__ ArcWalk walk_s[4];
     __shared__ T key_s[4][64];
     __shared__ unsigned hit_s[4][64];
     const unsigned w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint64_t* vend = vend_s[w]; uint64_t* base = base_s[w]; T* keys = key_s[w]; unsigned* hit = hit_s[w];
-    bool oob = false, wrote = false;
+    ArcWalk& walk = walk_s[w]; T* keys = key_s[w]; unsigned* hit = hit_s[w];
+    unsigned met = 0;                      // what this lane met (mOob, mWrote).  One word: see bvg_arcwalk.h on what a walk's functor captures
     for (int64_t x0 = ((int64_t)blockIdx.x * 4 + w) * 64; x0 < cnt; x0 += (int64_t)gridDim.x * 256) {   // (whole wavefronts: no workgroup barrier)
         const int64_t i = x0 + lane;
         const bool valid = i < cnt;
@@ -87,18 +86,11 @@ __global__ void __launch_bounds__(256) scc_sweep_kernel(const uint64_t* cum, int
             if (MODE == kBw && ku != none<T>() && (flags[u] & fBw)) ku = none<T>();
         }
         const bool act = ku != none<T>();
-        const uint64_t len = act ? e - b : 0;
-        uint64_t inc = len;
-        for (unsigned o = 1; o < 64; o <<= 1) { const uint64_t t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-        const uint64_t total = __shfl(inc, 63, 64);
+        const uint64_t total = walk.begin(lane, act, b, e, [&] { keys[lane] = ku; hit[lane] = 0; });
         if (total == 0) continue;                                            // (uniform: no list of this group takes part)
-        vend[lane] = inc; base[lane] = b - (inc - len); keys[lane] = ku; hit[lane] = 0;
-        __builtin_amdgcn_wave_barrier();                                     // (LDS operations of one wavefront complete in order)
-        for (uint64_t t = lane; t < total; t += 64) {
-            int l = 0, r = 63;                                               // first list whose end is > t (vend[63] = total > t)
-            while (l < r) { const int m = (l + r) >> 1; if (vend[m] <= t) l = m + 1; else r = m; }
-            const int64_t y = succ[base[l] + t];
-            if (y < 0 || y >= n) { oob = true; continue; }
+        walk.for_each_arc(lane, total, [&](int l, uint64_t at) {
+            const int64_t y = succ[at];
+            if (y < 0 || y >= n) { met |= mOob; return; }
             const T cu = keys[l];
             if (MODE == kTrim) {
                 if (y != lo + x0 + l && key[y] == cu) {
@@ -106,27 +98,27 @@ __global__ void __launch_bounds__(256) scc_sweep_kernel(const uint64_t* cum, int
                     if (!(flags[y] & fIn)) set_flag(flags, y, fIn);
                 }
             } else if (MODE == kFw) {
-                if (key[y] == cu && !(flags[y] & fFw)) { set_flag(flags, y, fFw); wrote = true; }
+                if (key[y] == cu && !(flags[y] & fFw)) { set_flag(flags, y, fFw); met |= mWrote; }
             } else if (MODE == kBw) {
                 if (!hit[l] && key[y] == cu && (flags[y] & fBw)) hit[l] = 1;
             } else if (MODE == kColour) {
                 const T cv = colour[y];
-                if (cv != none<T>() && cv < cu) { __hip_atomic_fetch_max(colour + y, cu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); wrote = true; }
+                if (cv != none<T>() && cv < cu) { __hip_atomic_fetch_max(colour + y, cu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); met |= mWrote; }
             } else {
                 const unsigned h = key[y] != cu ? fArc | fLeave : fArc;
                 if ((hit[l] & h) != h) atomicOr(hit + l, h);
             }
-        }
-        __builtin_amdgcn_wave_barrier();
+        });
+        __builtin_amdgcn_wave_barrier();                                     // (every lane's hit[] writes before the lists' own lanes read them)
         if (act && hit[lane]) {
             if (MODE == kTrim) set_flag(flags, u, fOut);
-            else if (MODE == kBw) { set_flag(flags, u, fBw); wrote = true; }
+            else if (MODE == kBw) { set_flag(flags, u, fBw); met |= mWrote; }
             else if (MODE == kBucket) { if ((flags[ku] & hit[lane]) != hit[lane]) set_flag(flags, (int64_t)ku, hit[lane]); }
         }
-        __builtin_amdgcn_wave_barrier();                                     // (the next group's LDS writes after every lane's reads)
+        walk.end();
     }
-    if (oob) atomicOr(ctl + kCtlBad, 1ull);
-    if (__ballot(wrote) && lane == 0 && ctl[kCtlChanged] == 0) atomicOr(ctl + kCtlChanged, 1ull);
+    if (met & mOob) atomicOr(ctl + kCtlBad, 1ull);
+    if (__ballot(met & mWrote) && lane == 0 && ctl[kCtlChanged] == 0) atomicOr(ctl + kCtlChanged, 1ull);
 }
 
 template <typename T> __global__ void scc_init_kernel(T* rep, T* colour, uint8_t* flags, int64_t n) {
@@ -230,7 +222,6 @@ template <typename T> struct SccRun {
     bvg_graph* g; bvghost::SweepPlan sp; int64_t n;
     T* rep; T* colour; uint8_t* flags; unsigned long long* ctl;
     uint64_t counters[BVG_SCC_COUNTERS] = {};
-    bool single = false, decoded = false;
     unsigned long long h[kCtlWords] = {};                                    // the control words as last read
 
     int zero_ctl() { HIPCHK(hipMemsetAsync(ctl, 0, kCtlWords * 8, g->stream)); return 0; }
@@ -240,12 +231,6 @@ template <typename T> struct SccRun {
         HIPCHK(hipStreamSynchronize(g->stream));
         return h[kCtlBad] ? BVG_E_EOF : 0;
     }
-    int load(const Batch& b) {
-        if (single && decoded) return 0;
-        const int rc = sp.decode(g, b); if (rc) return rc;
-        counters[kDecodes]++; decoded = true;
-        return 0;
-    }
     template <int MODE> void launch(const Batch& b) {
         const int64_t cnt = b.hi - b.lo;
         hipLaunchKernelGGL((scc_sweep_kernel<T, MODE>), dim3(grid(cnt, 256)), dim3(256), 0, g->stream, (const uint64_t*)sp.cum(), b.lo, cnt, (const int64_t*)sp.succ(), n,
@@ -253,7 +238,7 @@ template <typename T> struct SccRun {
     }
     // one complete sweep of a mode without a fixpoint (trim, buckets): nothing is read back
     template <int MODE> int sweep_plain() {
-        for (const Batch& b : sp.batches) { const int rc = load(b); if (rc) return rc; launch<MODE>(b); HIPCHK(hipGetLastError()); }
+        for (const Batch& b : sp.batches) { const int rc = sp.load(g, b, &counters[kDecodes]); if (rc) return rc; launch<MODE>(b); HIPCHK(hipGetLastError()); }
         counters[kSweeps]++;
         return 0;
     }
@@ -262,14 +247,14 @@ template <typename T> struct SccRun {
         for (bool wrote = true; wrote;) {
             wrote = false;
             for (const Batch& b : sp.batches) {
-                int rc = load(b); if (rc) return rc;
+                int rc = sp.load(g, b, &counters[kDecodes]); if (rc) return rc;
                 for (int run = 0;; run++) {
                     rc = zero_ctl(); if (rc) return rc;
                     launch<MODE>(b);
                     rc = read_ctl(); if (rc) return rc;
                     if (!h[kCtlChanged]) break;
                     wrote = true;
-                    if (single || run + 1 >= kMaxReruns) break;              // (one batch: the next launch IS the next sweep)
+                    if (sp.single() || run + 1 >= kMaxReruns) break;              // (one batch: the next launch IS the next sweep)
                 }
             }
             counters[kSweeps]++;
@@ -329,8 +314,7 @@ template <typename T> int scc_t(bvg_graph* g, uint32_t flags, int64_t* comp, int
     uint64_t per = 0;                                                       // (of what is free once the per-node arrays are there)
     int rc = arc_budget(n, kMaxBatchArcs, "BVG_SCC_BATCH_ARCS", &per); if (rc) return rc;
     rc = r.sp.build(g, per); if (rc) return rc;
-    r.single = r.sp.batches.size() == 1;
-    r.counters[kResident] = r.single ? 1 : 0;
+    r.counters[kResident] = r.sp.single() ? 1 : 0;
     uint64_t live = (uint64_t)n;
     {
         DevBuf ws;                                                          // (this scope: gone before the numbering pass, which needs the memory)

@@ -3,7 +3,7 @@
 // The reference makes one sequential pass over all successor lists (Stats.run, Stats.java:96-281).  Here the same numbers come from
 //   degrees   the outdegrees of all nodes (one code each, no list decoded): dangling nodes, min / max outdegree and their nodes, the
 //             outdegree distribution.  Every node is seen here, also those the batch plan of the sweep leaves out (runs of empty lists);
-//   sweep     the arc-bounded sweep of bvg_plan.hip; per batch one kernel with the lane-to-arc mapping of cc_hook_kernel: per list the
+//   sweep     the arc-bounded sweep of bvg_plan.hip; per batch one kernel with the lane-to-arc mapping of bvg_arcwalk.h: per list the
 //             gap terms and the d == 1 self-loops (terminal nodes), per arc (x, y) indegree[y] += 1, |y - x| into the locality sum, a
 //             loop or bin msb(|y - x|) of the 64-bin histogram;
 //   indegrees min / max with their nodes and the indegree distribution from the per-node counters.
@@ -22,6 +22,7 @@
 #include <cstring>
 #include <vector>
 
+#include "bvg_arcwalk.h"
 #include "bvg_host.h"
 #include "../../include/bvgraph_hip.h"
 
@@ -72,32 +73,28 @@ template <typename T, bool ELECT> __device__ __forceinline__ void scatter(T* ind
     }
 }
 
-// One wavefront per 64 consecutive nodes of the batch [lo, lo + cnt) (four per workgroup), as cc_hook_kernel: first the 64 lists' own
-// terms (one lane each), then the lanes walk the lists' arcs in chunks of 64; the owner of arc t is the number of list ends <= t.
-// The chunk loop is uniform (a lane without an arc stays in it), so the ballots see all 64 lanes.  A target outside [0, n) is a
-// malformed stream: flagged in acc[kBad] and not counted anywhere.
+// One wavefront per 64 consecutive nodes of the batch [lo, lo + cnt) (four per workgroup): first the 64 lists' own terms (one lane each),
+// then the lists' arcs, walked as bvg_arcwalk.h describes.  The walk is the uniform one (a lane without an arc stays in it), so the
+// ballots see all 64 lanes.  A target outside [0, n) is a malformed stream: flagged in acc[kBad] and not counted anywhere.
 template <typename T, bool ELECT> __global__ void __launch_bounds__(256) stats_sweep_kernel(const uint64_t* cum, int64_t lo, int64_t cnt, const int64_t* succ, int64_t n,
                                                                                             T* indeg, unsigned long long* acc) {
-    __shared__ uint64_t ends_s[4][64];
+    __shared__ ArcWalk walk_s[4];
     __shared__ unsigned long long part_s[4][kPartWords + 1];
     __shared__ unsigned long long bins_s[64];
     const unsigned w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    ArcWalk& walk = walk_s[w];
     if (threadIdx.x < 64) bins_s[threadIdx.x] = 0;
     __syncthreads();
     unsigned long long loops = 0, term1 = 0, ngaps = 0, bin = 0;           // bin: the arcs of histogram bin `lane`
     U128 gap{0, 0}, loc{0, 0};
     bool oob = false;
     for (int64_t x0 = ((int64_t)blockIdx.x * 4 + w) * 64; x0 < cnt; x0 += (int64_t)gridDim.x * 256) {   // (whole wavefronts: no workgroup barrier)
-    const int64_t xe = x0 + 64 < cnt ? x0 + 64 : cnt;
-    const int c = (int)(xe - x0);
-    uint64_t* ends = ends_s[w];
-    const uint64_t a0 = cum[x0], a1 = cum[xe];
-    if ((int)lane < c) {
-        const uint64_t b = cum[x0 + lane], e = cum[x0 + lane + 1];
-        ends[lane] = e;
+        const int64_t i = x0 + lane;
+        const bool valid = i < cnt;
+        const uint64_t b = valid ? cum[i] : 0, e = valid ? cum[i + 1] : 0;
         const uint64_t d = e - b;
         if (d) {
-            const int64_t x = lo + x0 + lane, first = succ[b];
+            const int64_t x = lo + i, first = succ[b];
             if (d == 1) term1 += first == x ? 1 : 0;
             else {                                                          // Stats.java:124-128: d, not d - 1; a list of one arc adds nothing
                 const int64_t last = succ[e - 1], v = first - x;
@@ -106,31 +103,27 @@ template <typename T, bool ELECT> __global__ void __launch_bounds__(256) stats_s
                 gap.add(v >= 0 ? (unsigned long long)v << 1 : (((unsigned long long)(-(v + 1))) << 1) + 1);   // Fast.int2nat
             }
         }
-    }
-    __builtin_amdgcn_wave_barrier();                                    // (LDS operations of one wavefront complete in order)
-    for (uint64_t t0 = a0; t0 < a1; t0 += 64) {
-        const uint64_t t = t0 + lane;
-        const bool has = t < a1;
-        int l = 0, r = c;
-        while (l < r) { const int m = (l + r) >> 1; if (ends[m] <= t) l = m + 1; else r = m; }
-        const int64_t x = lo + x0 + l;
-        const int64_t y = has ? succ[t] : 0;
-        const bool ok = has && y >= 0 && y < n;
-        oob |= has && !ok;
-        scatter<T, ELECT>(indeg, y, ok, lane);
-        const unsigned long long dist = ok ? (unsigned long long)(y > x ? y - x : x - y) : 0ull;
-        loc.add(dist);
-        loops += ok && dist == 0 ? 1 : 0;
-        const bool nl = ok && dist != 0;
-        const unsigned b = nl ? 63u - (unsigned)__builtin_clzll(dist) : 0u;
-        uint64_t mine = __ballot(nl);                                      // the lanes whose arc falls into bin `lane`
-        for (int k = 0; k < 6; k++) {
-            const uint64_t mk = __ballot(nl && ((b >> k) & 1u));
-            mine &= (lane >> k) & 1u ? mk : ~mk;
-        }
-        bin += (unsigned long long)__builtin_popcountll(mine);
-    }
-    __builtin_amdgcn_wave_barrier();                                    // (the next group's LDS writes after every lane's reads)
+        const uint64_t total = walk.begin(lane, d != 0, b, e, [] {});
+        if (total == 0) continue;                                            // (uniform: no list of this group has an arc)
+        walk.for_each_chunk(lane, total, [&](bool has, int l, uint64_t at) {
+            const int64_t x = lo + x0 + l;
+            const int64_t y = has ? succ[at] : 0;
+            const bool ok = has && y >= 0 && y < n;
+            oob |= has && !ok;
+            scatter<T, ELECT>(indeg, y, ok, lane);
+            const unsigned long long dist = ok ? (unsigned long long)(y > x ? y - x : x - y) : 0ull;
+            loc.add(dist);
+            loops += ok && dist == 0 ? 1 : 0;
+            const bool nl = ok && dist != 0;
+            const unsigned bn = nl ? 63u - (unsigned)__builtin_clzll(dist) : 0u;
+            uint64_t mine = __ballot(nl);                                    // the lanes whose arc falls into bin `lane`
+            for (int k = 0; k < 6; k++) {
+                const uint64_t mk = __ballot(nl && ((bn >> k) & 1u));
+                mine &= (lane >> k) & 1u ? mk : ~mk;
+            }
+            bin += (unsigned long long)__builtin_popcountll(mine);
+        });
+        walk.end();
     }
     // wavefront -> workgroup (LDS) -> one global atomic per counter
     loops = wave_sum(loops); term1 = wave_sum(term1); ngaps = wave_sum(ngaps);
