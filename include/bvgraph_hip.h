@@ -458,6 +458,82 @@ int bvg_store(const bvg_params* p, int64_t nodes, const uint64_t* adj_off, const
               uint8_t** graph, uint64_t* graph_bytes, uint64_t** offsets);
 void bvg_free(void* p);
 
+/* ---- EFGraph: the quasi-succinct (Elias-Fano) graph format (EFGraph.java, "EF" below) ----
+ * basename.properties: graphclass it.unimi.dsi.big.webgraph.EFGraph (it.unimi.dsi.webgraph.EFGraph accepted, EF:683), version <= 0
+ * (EF:686-687), nodes, arcs, upperbound (default nodes, EF:690), quantum (a power of two, EF:691-693), byteorder (LITTLE_ENDIAN /
+ * BIG_ENDIAN, EF:695-698).  basename.graph: 64-bit words in that byte order; bit p of the stream is bit p & 63 of word p >> 6 (least
+ * significant bit first, LongWordOutputBitStream EF:294-414 -- the opposite of BVGraph); close() always writes the current word
+ * (EF:408-413), so the file holds bits / 64 + 1 words.  basename.offsets: nodes + 1 delta-coded gaps in an ordinary MSB-first stream,
+ * the first being 0 (EF:785, EF:812): bvg_decode_offsets(.., BVG_DELTA, ..) reads it.
+ * Record of a node with outdegree d, upper bound U, quantum 2^q; the list gets a terminator equal to U, so L = d + 1 (EF:803, EF:522):
+ *   l = max(0, msb(U / L)) (EF:140-142), ps = max(0, ceilLog2(L + (U >> l))) (EF:152-154), P = (U >> l) >> q (EF:165-168)
+ *   gamma(d) | P pointers of ps bits | L lower fields of l bits | (U >> l) + d + 1 upper bits
+ *   gamma(x) (EF:394-406): v = x + 1, m = msb(v): m zero bits, a one bit, the low m bits of v.  Element i (e_d = U): lower field e_i & (2^l - 1),
+ *   upper bit (e_i >> l) + i set.  Pointer k (from 1) = k 2^q + #{i : (e_i >> l) < k 2^q}: the position just past the (k 2^q)-th zero (EF:511-513).
+ * So a record's length is a closed form of d, element i is (select1(upper, i) - i) << l | lower[i], and nothing is a chain.
+ * Conventions are those of the bvg_ entry points above: 0 or a negative bvg_status, caller-allocated host buffers unless the name ends in
+ * _dev, one handle not re-entrant, bvg_ef_copy() flyweights for other threads.  Not built: multi-GPU shards, node bases, 32-bit successor
+ * output, the analytics on an EFGraph, the cached offsets list (basename.obl, EF:723-735). */
+typedef struct bvg_ef_params {          /* 32 bytes */
+    int64_t nodes;
+    int64_t arcs;                       /* -1 if the properties do not say */
+    int64_t upper_bound;                /* >= nodes */
+    int32_t log2_quantum;               /* 0..62 */
+    int32_t big_endian;                 /* byte order of the words of the FILE: swapped once at load, the device holds little-endian words */
+} bvg_ef_params;
+typedef struct bvg_efgraph bvg_efgraph;
+/* EFGraph.loadInternal's property checks (EF:675-698): BVG_E_IO for another class, a missing or newer version, missing nodes / quantum /
+ * byteorder; BVG_E_ARG (IllegalArgumentException) for a quantum that is no power of two, an unknown byte order, upperbound < nodes. */
+int bvg_ef_parse_properties(const char* text, size_t len, bvg_ef_params* out);
+/* Host only: the nodes + 1 offsets of a bare stream by one walk (gamma, the closed-form length, repeat): what a load without
+ * basename.offsets derives.  BVG_E_EOF for a record that runs past the stream, BVG_E_UNSUPPORTED for an outdegree of 2^31 or more. */
+int bvg_ef_derive_offsets(const bvg_ef_params* p, const uint8_t* bytes, uint64_t nbytes, uint64_t* out);
+/* EFGraph.load / loadMapped / loadOffline / loadSequential (EF:542-673).  BVG_LOAD_SEQUENTIAL / _OFFLINE do not read basename.offsets:
+ * the offsets are derived on the host (serial, a few operations per node). */
+int bvg_ef_open(const char* basename, int load_mode, int device, bvg_efgraph** out);
+/* Same from host memory; bytes in the byte order p says.  offsets: nodes + 1 bit positions, or NULL (derived).  Offsets given by the
+ * caller are checked where they are used: every call verifies, for the nodes it touches and before it writes anything, that
+ * offsets[x + 1] - offsets[x] is the closed-form length of the record at offsets[x] and that the record ends inside the stream;
+ * a mismatch is BVG_E_EOF and nothing is written for that call. */
+int bvg_ef_open_mem(const bvg_ef_params* p, const uint8_t* bytes, uint64_t nbytes, const uint64_t* offsets, int device, bvg_efgraph** out);
+/* Same from DEVICE memory: little-endian words (nbytes a multiple of 8, p->big_endian 0) adopted, not copied -- they must stay alive
+ * until the last handle closes; d_offsets (nodes + 1 uint64) is copied and may be freed when the call returns. */
+int bvg_ef_open_dev(const bvg_ef_params* p, const void* d_words, uint64_t nbytes, const void* d_offsets, int device, bvg_efgraph** out);
+int bvg_ef_copy(const bvg_efgraph* g, bvg_efgraph** out);      /* EFGraph.copy() (EF:1173-1176) */
+void bvg_ef_close(bvg_efgraph* g);
+int bvg_ef_info(const bvg_efgraph* g, bvg_ef_params* out);
+int bvg_ef_get_offsets(bvg_efgraph* g, uint64_t* out);         /* nodes + 1 entries */
+/* outdegree(x) for x in [from, to) (EF:1008-1014). */
+int bvg_ef_outdegrees(bvg_efgraph* g, int64_t from, int64_t to, int32_t* out);
+/* The successors of nodes [from, to) (EF:1081-1095 per list), with the capacity contract of bvg_decode_range: BVG_E_CAPACITY and
+ * *n_succ = the size needed when succ_cap is smaller (succ may be NULL to query); outdeg may be NULL.  A record that fails the length
+ * check (above), or whose outdegree is 2^31 or more (BVG_E_UNSUPPORTED), fails the call before anything is written.  An upper-bits
+ * region that does not hold exactly d + 1 ones is BVG_E_EOF with the slots of the missing ones written as -1 and every other list of
+ * the call intact; no write ever leaves a list's own d slots. */
+int bvg_ef_decode_range(bvg_efgraph* g, int64_t from, int64_t to, int32_t* outdeg, int64_t* succ, uint64_t succ_cap, uint64_t* n_succ);
+int bvg_ef_decode_range_dev(bvg_efgraph* g, int64_t from, int64_t to, void* d_outdeg, void* d_succ, uint64_t succ_cap, uint64_t* n_succ);
+/* successors(x) for nodes[count] in any order, repeats allowed; lists concatenated in request order.  A node outside [0, nodes): BVG_E_ARG. */
+int bvg_ef_successors_batch(bvg_efgraph* g, const int64_t* nodes, int64_t count, int32_t* outdeg, int64_t* succ, uint64_t succ_cap, uint64_t* n_succ);
+/* The scan of [from, to) consumed on chip under the contract of bvg_scan: chk = the sum of bvg_arc_mix over the arcs, one multiply-add
+ * per produced successor, so {nodes, arcs, chk} equal bvg_scan of the same graph stored as a BVGraph.  graph_bytes = the bytes of the
+ * words covering the range, index_bytes = the offsets read, kernel_ms = from the header kernel to the last decode kernel (one host
+ * round trip for the sizes included), launches; every other field is 0. */
+int bvg_ef_scan(bvg_efgraph* g, int64_t from, int64_t to, bvg_scan_result* out);
+/* LazyLongSkippableIterator.skipTo(bounds[i]) on a FRESH iterator over successors(nodes[i]) (EF:1098-1160): out[i] = the smallest
+ * successor >= bounds[i], or -1.  The result is defined on the d real successors only (the reference compares the terminator with
+ * nodes, EF:1106, EF:1157, and so hands out a terminator upperbound != nodes as if it were a successor).  When (bound >> l) exceeds the
+ * quantum the walk starts at skip pointer (bound >> l) >> q.  A node outside [0, nodes): BVG_E_ARG; a bad record: BVG_E_EOF and out untouched. */
+int bvg_ef_skip_to_batch(bvg_efgraph* g, const int64_t* nodes, const int64_t* bounds, int64_t count, int64_t* out);
+/* hipEvent time of the kernel of the last bvg_ef_skip_to_batch (or of the last bvg_ef_scan) on this handle: measurements only. */
+int bvg_ef_last_kernel_ms(bvg_efgraph* g, double* ms);
+/* EFGraph.store (EF:773-820) on the device, from an adjacency in CSR form as bvg_store takes it, with the same checks (BVG_E_ARG, nothing
+ * written: offsets that do not start at 0, decrease or span more than 2^31 - 1 successors; lists that are not strictly increasing or
+ * leave [0, nodes)) and upper_bound >= nodes, 0 <= log2_quantum <= 62 besides.  *graph = the bytes of basename.graph in the byte order
+ * asked for, the trailing word included (*graph_bytes = 8 (bits / 64 + 1)); *offsets = nodes + 1 bit positions (write basename.offsets
+ * from their delta-coded gaps).  Both malloc'ed (bvg_free). */
+int bvg_ef_store(int64_t nodes, int64_t upper_bound, int log2_quantum, int big_endian, const uint64_t* adj_off, const int64_t* adj, int device,
+                 uint8_t** graph, uint64_t* graph_bytes, uint64_t** offsets);
+
 /* ---- synthetic-workload helper (bench only): K back-to-back copies of the graph ----
  * BV records are translation invariant (every value is coded relative to the node id, Appendix A.3
  * of SURVEY.md), so the concatenation of K copies of the bit stream is a valid BVGraph with K*nodes

@@ -109,6 +109,28 @@ def stats_signatures():
             "bvg_stats_indegrees_dev": [vp, i64, i64, vp]}
 
 
+class EFParams(C.Structure):
+    """bvg_ef_params (32 bytes)."""
+    _fields_ = [("nodes", C.c_int64), ("arcs", C.c_int64), ("upper_bound", C.c_int64), ("log2_quantum", C.c_int32), ("big_endian", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def ef_signatures():
+    """argtypes of the bvg_ef_* entry points (EFGraph), by name."""
+    vp, i64, u64, pp, ci = C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(C.c_void_p), C.c_int
+    P = C.POINTER(EFParams)
+    return {"bvg_ef_parse_properties": [C.c_char_p, C.c_size_t, P], "bvg_ef_derive_offsets": [P, vp, u64, vp],
+            "bvg_ef_open": [C.c_char_p, ci, ci, pp], "bvg_ef_open_mem": [P, vp, u64, vp, ci, pp], "bvg_ef_open_dev": [P, vp, u64, vp, ci, pp],
+            "bvg_ef_copy": [vp, pp], "bvg_ef_close": [vp], "bvg_ef_info": [vp, P], "bvg_ef_get_offsets": [vp, vp],
+            "bvg_ef_outdegrees": [vp, i64, i64, vp], "bvg_ef_decode_range": [vp, i64, i64, vp, vp, u64, C.POINTER(u64)],
+            "bvg_ef_decode_range_dev": [vp, i64, i64, vp, vp, u64, C.POINTER(u64)],
+            "bvg_ef_successors_batch": [vp, vp, i64, vp, vp, u64, C.POINTER(u64)], "bvg_ef_scan": [vp, i64, i64, C.POINTER(ScanResult)],
+            "bvg_ef_skip_to_batch": [vp, vp, vp, i64, vp], "bvg_ef_last_kernel_ms": [vp, C.POINTER(C.c_double)],
+            "bvg_ef_store": [i64, i64, ci, ci, vp, vp, ci, pp, C.POINTER(u64), pp]}
+
+
 OK, E_ARG, E_STATE, E_UNSUPPORTED, E_IO, E_EOF, E_NOMEM, E_HIP, E_CAPACITY = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 

@@ -451,4 +451,80 @@ public:
     }
 };
 
+// EFGraph.java: the quasi-succinct format, decoded on the device (bvg_ef_*).  successors(x) is a LazyLongSkippableIterator over the
+// node's list (skipTo on the host copy); skipTo(nodes, bounds) is the batched device form: for each pair, skipTo(bound) on a fresh
+// iterator (EFGraph.java:1098-1160), defined on the real successors only.  store: EFGraph.store (:773-820) on the device.
+class LazyLongSkippableIterator {
+    std::vector<int64_t> a_; size_t i_ = 0; int64_t last_ = INT64_MIN;
+public:
+    static constexpr int64_t END_OF_LIST = INT64_MAX;
+    explicit LazyLongSkippableIterator(std::vector<int64_t> a) : a_(std::move(a)) {}
+    int64_t nextLong() { if (i_ < a_.size()) return last_ = a_[i_++]; last_ = END_OF_LIST; return -1; }
+    int64_t skipTo(int64_t lowerBound) {                                                       // LazyLongSkippableIterator.java
+        if (lowerBound <= last_) return last_;
+        while (i_ < a_.size() && a_[i_] < lowerBound) i_++;
+        return last_ = i_ < a_.size() ? a_[i_++] : END_OF_LIST;
+    }
+};
+
+class EFGraph {
+    bvg_efgraph* h_ = nullptr; bvg_ef_params p_{}; std::string basename_;
+    explicit EFGraph(bvg_efgraph* h) : h_(h) { check(bvg_ef_info(h_, &p_), "ef_info"); }
+public:
+    ~EFGraph() { bvg_ef_close(h_); }
+    EFGraph(const EFGraph&) = delete;
+    static std::shared_ptr<EFGraph> load(const std::string& basename, int device = 0, int mode = BVG_LOAD_STANDARD) {       // EFGraph.java:542-750
+        bvg_efgraph* h = nullptr; check(bvg_ef_open(basename.c_str(), mode, device, &h), "EFGraph.load");
+        auto g = std::shared_ptr<EFGraph>(new EFGraph(h)); g->basename_ = basename; return g;
+    }
+    static std::shared_ptr<EFGraph> loadOffline(const std::string& b, int device = 0) { return load(b, device, BVG_LOAD_OFFLINE); }
+    static std::shared_ptr<EFGraph> fromMemory(const bvg_ef_params& p, const uint8_t* bytes, uint64_t nbytes, const uint64_t* offsets, int device = 0) {
+        bvg_efgraph* h = nullptr; check(bvg_ef_open_mem(&p, bytes, nbytes, offsets, device, &h), "ef_open_mem");
+        return std::shared_ptr<EFGraph>(new EFGraph(h));
+    }
+    bvg_efgraph* handle() const { return h_; }
+    int64_t numNodes() const { return p_.nodes; }
+    int64_t numArcs() const { if (p_.arcs < 0) throw UnsupportedOperation("numArcs"); return p_.arcs; }
+    int64_t upperBound() const { return p_.upper_bound; }
+    int log2Quantum() const { return p_.log2_quantum; }
+    bool randomAccess() const { return true; }
+    const std::string& basename() const { return basename_; }
+    std::shared_ptr<EFGraph> copy() const {                                                    // EFGraph.java:1173-1176
+        bvg_efgraph* h = nullptr; check(bvg_ef_copy(h_, &h), "ef_copy");
+        auto g = std::shared_ptr<EFGraph>(new EFGraph(h)); g->basename_ = basename_; return g;
+    }
+    int64_t outdegree(int64_t x) {                                                             // EFGraph.java:1008-1014
+        if (x < 0 || x >= p_.nodes) throw std::invalid_argument("Node index out of range");
+        int32_t d; check(bvg_ef_outdegrees(h_, x, x + 1, &d), "ef_outdegree"); return d;
+    }
+    void decodeRange(int64_t from, int64_t to, std::vector<int32_t>& deg, std::vector<int64_t>& succ) {
+        deg.resize((size_t)(to > from ? to - from : 0));
+        uint64_t need = 0;
+        int st = bvg_ef_decode_range(h_, from, to, deg.data(), nullptr, 0, &need);
+        if (st != BVG_E_CAPACITY) check(st, "ef_decode_range");
+        succ.resize((size_t)need);
+        if (need) check(bvg_ef_decode_range(h_, from, to, deg.data(), succ.data(), need, &need), "ef_decode_range");
+    }
+    LazyLongSkippableIterator successors(int64_t x) {                                          // EFGraph.java:1168-1171
+        if (x < 0 || x >= p_.nodes) throw std::invalid_argument("Node index out of range");
+        std::vector<int32_t> d; std::vector<int64_t> s; decodeRange(x, x + 1, d, s); return LazyLongSkippableIterator(std::move(s));
+    }
+    std::vector<int64_t> skipTo(const std::vector<int64_t>& nodes, const std::vector<int64_t>& bounds) {
+        if (nodes.size() != bounds.size()) throw std::invalid_argument("skipTo: one bound per node");
+        std::vector<int64_t> out(nodes.size());
+        if (!nodes.empty()) check(bvg_ef_skip_to_batch(h_, nodes.data(), bounds.data(), (int64_t)nodes.size(), out.data()), "ef_skip_to_batch");
+        return out;
+    }
+    bvg_scan_result scan(int64_t from = 0, int64_t to = -1) { bvg_scan_result r; check(bvg_ef_scan(h_, from, to < 0 ? p_.nodes : to, &r), "ef_scan"); return r; }
+    static void store(const std::vector<uint64_t>& adjOff, const std::vector<int64_t>& adj, int64_t upperBound, int log2Quantum, bool bigEndian,
+                      std::vector<uint8_t>& graph, std::vector<uint64_t>& offsets, int device = 0) {
+        uint8_t* g = nullptr; uint64_t nb = 0; uint64_t* o = nullptr;
+        const int64_t n = (int64_t)adjOff.size() - 1;
+        static const int64_t none = 0;
+        check(bvg_ef_store(n, upperBound, log2Quantum, bigEndian ? 1 : 0, adjOff.data(), adj.empty() ? &none : adj.data(), device, &g, &nb, &o), "ef_store");
+        graph.assign(g, g + nb); offsets.assign(o, o + n + 1);
+        bvg_free(g); bvg_free(o);
+    }
+};
+
 }  // namespace webgraph
