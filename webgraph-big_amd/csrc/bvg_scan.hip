@@ -587,7 +587,15 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
         const bool on1 = needed && lane < K1;
         const uint32_t tqp = BVG_T0();
         uint64_t refmask = 0;
-        for (uint32_t r = 1; r <= W && r < 64; r++) refmask |= ballot(parse && ref == r) >> r;
+        // (not in the 85-VGPR instantiation: the register it holds across the sub-rows spills there -- 39 spilled VGPRs against 25, the tiled cnr-2000 -2.2 %,
+        //  profiles/levels_ab_cnr.txt -- and the short lists of a sparse graph seldom fill the pool)
+        constexpr bool LIVE = OCC <= 5;
+        uint32_t lastref = 0;                                                 // the largest distance at which a lane of this super-row copies from my list (64: the next super-row does)
+        for (uint32_t r = 1; r <= W && r < 64; r++) {
+            const uint64_t m = ballot(parse && ref == r) >> r;
+            refmask |= m;
+            if (LIVE) lastref = ((m >> lane) & 1ull) ? r : lastref;
+        }
         if (K1 != K1win) {
             const int64_t nx = r0 + K1 + lane;
             nxt_off = 0; nxt_end = 0;
@@ -596,6 +604,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
         // The last W nodes of the super-row can be referenced by the first W nodes of the next one: peek at those records' references
         // (outdegree gamma, reference unary: BVG:654-660, 692-703) when they lie inside the staged window; otherwise, assume they are.
         // Nodes of the next BLOCK do not count: that block decodes its halo itself.
+        uint64_t nextmask = 0;
         {
             uint32_t tgt = 64;                                                // lane of this super-row that my peeked node references
             bool unknown = false;
@@ -632,11 +641,13 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
                     }
                 }
             }
-            if (ballot(unknown)) refmask |= K1 >= W ? (~0ull << (K1 - W)) : ~0ull;
-            for (uint32_t j = 0; j < W && j < 64; j++) { const uint32_t t = lane_get(tgt, j); if (t < 64) refmask |= 1ull << t; }
+            if (ballot(unknown)) nextmask |= K1 >= W ? (~0ull << (K1 - W)) : ~0ull;
+            for (uint32_t j = 0; j < W && j < 64; j++) { const uint32_t t = lane_get(tgt, j); if (t < 64) nextmask |= 1ull << t; }
+            refmask |= nextmask;
         }
         BVG_T1(15, tqp);
         const bool copied_from = (refmask >> lane) & 1ull;
+        if (LIVE && ((nextmask >> lane) & 1ull)) lastref = 64;                          // the next super-row copies from it (or may): no sub-row of this one ends behind lane + 64
         BVG_WC(12, __popcll(ballot(copied_from && on1)));                     // (work-count build: stored lists | reference-free with intervals | with reference and extras | direct)
         BVG_WC(13, __popcll(ballot(copied_from && on1 && ref == 0 && ic != 0)));
         BVG_WC(9, __popcll(ballot(copied_from && on1 && ref != 0 && (ic != 0 || nres != 0))));
@@ -882,15 +893,24 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
             const bool emitn = act && d > 0;
             // ---- level-synchronous emission by POSITION of the stored lists (as in bvg_rows.hip; no overlap checks: validated)
             const bool inrow = act && ref > 0 && ref + sa <= lane;                // the referenced list belongs to this sub-row
+            // A chain root that was decoded straight into place is no member of any level: a `direct` one is complete since the wave_sync() above, a `d2` one as soon
+            // as its intervals are filled in.  Who copies from such a root does not wait a level for it (with maxRef = 3 a sub-row then runs two levels, not three).
+            const bool rootdone = act && stored && ref == 0 && (direct || d2);
+            const int uplane = inrow ? (int)(lane - ref) : (int)lane;
+            const uint32_t updone = (uint32_t)__shfl((int)(rootdone ? (d2 ? 2 : 1) : 0), uplane, 64);   // (executed by every lane) 2: the root still owes its intervals
+            const bool waits = inrow && updone == 0u;                         // the referenced list is built by a level of this sub-row
             uint32_t lvl = 0;
             for (int it = 0; it < 64; it++) {
-                const uint32_t up = __shfl(lvl, inrow ? (int)(lane - ref) : (int)lane, 64);
-                const uint32_t nl = inrow ? up + 1 : 0;
+                const uint32_t up = __shfl(lvl, uplane, 64);
+                const uint32_t nl = waits ? up + 1 : 0;
                 const bool ch = nl != lvl; lvl = nl;
                 if (!ballot(ch)) break;
             }
+            const bool fills = act && d2;                                     // their intervals are written by an extras pass: the one of level 0, or ...
+            // ... a pass of their own in front of the levels (kFillPass) when a list of this sub-row copies from one of them: it needs the intervals in place
+            constexpr uint32_t kFillPass = 0xFFFFFFFFu;                       // (the level counter wraps from it to level 0)
             const bool emits = emitn && (stored || gl) && !direct && !d2;
-            const bool fills = act && d2;                                     // their intervals are written by the extras pass of level 0
+            const uint32_t Lfill = ballot(emits && inrow && updone == 2u) ? kFillPass : 0u;   // (a leaf is summed behind the last level: it waits for nobody)
             if (emits) pool[rtb + nres] = sentinel<T>();                      // guard behind the node's residual positions
             uint64_t remaining = ballot(emits || fills);
             wave_sync();
@@ -899,12 +919,12 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
             const bool wwn = wwon && emits && ref > 0 && d <= kWWBits && rlenS <= kWWBits && d >= (a.dbg >> 16);   // (bits 16.. of BVG_DBG: the shortest list built this way)
             bool wwbad = false;
             uint64_t wsum = 0;
-            for (uint32_t L = 0; remaining; L++) {
-                const bool memall = emits && lvl == L, memf = fills && L == 0;
+            for (uint32_t L = Lfill; remaining; L++) {
+                const bool memall = emits && lvl == L, memf = fills && L == Lfill;
                 const bool mem = memall && !wwn, memw = memall && wwn;
                 remaining &= ~ballot(memall || memf);
                 if (!ballot(memall || memf)) continue;
-                BVG_WC(0, 1);
+                BVG_WC(0, L == kFillPass ? 0 : 1);                           // (the fill pass is no level: it shows as a Z1 pass)
                 if (ballot(mem || memf)) {
                 // ZE: a bit vector per member (one bit per element of the list being built + a clear word behind it), all zero before the extras pass
                 uint32_t ebase = 0; bool zel = false;
@@ -1052,7 +1072,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
                     wave_sync();
                 }
                 blk_chk += zsum;
-                } else {
+                } else if (ballot(mem)) {                                      // (a pass of interval fills alone has no position task)
                 // ---------------- Z2: tasks of S output positions, all equally long
                 // S in one step: sum_i ceil(d_i / S) <= W / S + N - N / S < 64 once S >= W / (64 - N)  (N lists, W positions in all)
                 const uint32_t Wl = wave_sum32(mem ? d : 0u), Nl = (uint32_t)__popcll(ballot(mem));
@@ -1374,8 +1394,10 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
                     for (uint32_t t = lane; t < dd; t += 64) dst[t] = (int64_t)((uint64_t)pool[sb0 + t] + nbase);
                 }
                 if (rep && a.outdeg) a.outdeg[x - a.from] = (int32_t)d;
-                if (act && stored && !copied_from) nd_base[(uint32_t)x & RM] = (uint16_t)kNoList;   // nobody copies from it: the next compaction drops it
             }
+            // A list whose last referencer has run is dead: every reference of the super-row is known, and so is what the next one copies from.  The next compaction
+            // drops it -- lists of earlier sub-rows of this super-row too, whose last referencer sat in this one (MAT: and a list that was stored only to be copied out).
+            if (LIVE && on1 && stored && lane + lastref < se) nd_base[(uint32_t)x & RM] = (uint16_t)kNoList;
             wave_sync();
             sa = se;
             if (sa < K1) compact(r0 + (int64_t)sa);                            // the next sub-row starts from the stored lists of the W nodes before it
