@@ -534,6 +534,81 @@ int bvg_ef_last_kernel_ms(bvg_efgraph* g, double* ms);
 int bvg_ef_store(int64_t nodes, int64_t upper_bound, int log2_quantum, int big_endian, const uint64_t* adj_off, const int64_t* adj, int device,
                  uint8_t** graph, uint64_t* graph_bytes, uint64_t** offsets);
 
+/* ---- text graphs: ASCIIGraph (ASCIIGraph.java, "AG") and arc lists (ArcListASCIIGraph.java, "AL"; ScatteredArcsASCIIGraph.java) ----
+ * basename.graph-txt: the node count n on a line of its own, then one line per node holding its successors in increasing order, each
+ * followed by one space (AG:259-260).  An arc list: one `source TAB target` line per arc (AL:311).
+ * READING, both formats.  Line breaks are "\n", "\r\n" and a lone "\r": a '\r' always breaks a line, a '\n' does unless the byte before
+ * it is '\r'.  Every other byte of value 0..32 separates tokens; digits form numbers, with any number of leading zeros, at most 19
+ * significant digits and a value of at most 2^63 - 1; every other byte ('-', '.', '/', '#', quotes, letters, bytes >= 128) is refused.
+ * DELIBERATE DEVIATIONS: the reference reads numbers through a double ((long)st.nval): it accepts "3.0", loses exactness past 2^53 and
+ * treats '/' as a comment -- here integers are read exactly and the rest is refused; Long.parseLong accepts a signed header -- here
+ * digits only.
+ * An ASCIIGraph: the first line is n, digits and nothing else; the next n lines are the lists; bytes behind line n + 1 are never looked
+ * at (the reference never reads them; a header "0" may even lack its line break).  Refused, with *err = {byte offset, 1-based line,
+ * reason} of the SMALLEST byte offset at which anything is wrong (at one offset: the smallest reason):
+ *   BVG_TEXT_BAD_BYTE        BVG_E_IO   a byte that is no digit, separator or line break; at that byte
+ *   BVG_TEXT_BAD_HEADER      BVG_E_IO   a separator inside the header line (at it), or an empty header line (at byte 0)
+ *   BVG_TEXT_TOO_LARGE       BVG_E_IO   more than 19 significant digits, or a value above 2^63 - 1; at the first byte of the number
+ *   BVG_TEXT_NOT_NODE        BVG_E_IO   a successor >= n (AG:180); at the first byte of the number
+ *   BVG_TEXT_NOT_INCREASING  BVG_E_ARG  a successor not above the one before it on its line (the reference does not check, every
+ *                                       consumer here demands it); at the first byte of the second number
+ *   BVG_TEXT_EOF             BVG_E_IO   fewer than n complete lines behind the header -- a last line without its line break is incomplete,
+ *                                       the reference meets EOF inside it; at byte offset nbytes, on the line the text ends in
+ * An arc list: every line holds two numbers or none; a line whose first byte is '#' is skipped whole (ScatteredArcsASCIIGraph); `shift` is
+ * added to both ends; sources in any order; a duplicate arc appears once; nodes = max(largest id + 1, min_nodes); an empty text gives
+ * min_nodes nodes and no arcs.  BVG_TEXT_SYMMETRIZE adds the reverse of every arc, BVG_TEXT_NO_LOOPS drops the arcs x -> x (the two
+ * switches of ScatteredArcsASCIIGraph); unknown flag bits: BVG_E_ARG.  Not built: identifiers that are not node numbers.  Refused besides
+ * BVG_TEXT_BAD_BYTE and BVG_TEXT_TOO_LARGE:
+ *   BVG_TEXT_SHIFT_RANGE     BVG_E_ARG  id + shift below 0 or above 2^63 - 1 (AL:157); at the first byte of the number (a shift of -2^63 is
+ *                                       BVG_E_ARG for every entry point that takes one, before anything is read)
+ *   BVG_TEXT_ARC_FIELDS      BVG_E_IO   a line with one number (at the line break that ends it; at nbytes when none does) or with
+ *                                       three or more (at the first byte of the third)
+ * Ids of 2^40 or more are BVG_E_NOMEM: adj_off alone would not fit.
+ * DEVICE MEMORY.  The text and its CSR must fit on the device together: 1 byte per text byte (none for the _dev forms, which read the
+ * caller's buffer), 8 bytes per number and 8 per line break while parsing, and 16 bytes per 4 KiB of text; a text of single-digit
+ * successors therefore peaks near 5 bytes per text byte, a text of empty lines at 9.  An arc list takes, while it is sorted, 44 bytes per
+ * arc on top (88 with BVG_TEXT_SYMMETRIZE) plus the sort's own workspace.  What stays in the object: 8 (nodes + 1) + 8 arcs (an
+ * ASCIIGraph keeps the array of all its numbers: 8 bytes more, and 8 per number behind line n + 1).  BVG_E_NOMEM leaves nothing allocated.
+ * *out is NULL after every failure; err may be NULL.  One text of 8 TiB or more, or an arc list of 2^31 pairs or more (2^30 with
+ * BVG_TEXT_SYMMETRIZE): BVG_E_UNSUPPORTED.
+ * bvg_text_get / _get_dev: adj_off[nodes + 1] and adj[arcs] (sizes from bvg_text_info); either may be NULL; a capacity (in elements) below
+ * the size: BVG_E_CAPACITY, nothing written.  bvg_text_store: bvg_store on the resident CSR, no host round trip, the same bytes.
+ * WRITING.  bvg_text_format_ascii: for each node of [from, to) every successor in decimal followed by one space, then '\n' -- AG:259-260
+ * without the header line, which the file writer puts first.  bvg_text_format_arcs: (s + shift) TAB (t + shift) '\n' per arc (AL:311).  Node
+ * ids include the handle's node base.  bvg_text_format_csr: the same for an adjacency in host memory that came from elsewhere (kind =
+ * BVG_TEXT_ASCII / BVG_TEXT_ARCS; node x of the array is node first_node + x; adj_off may start anywhere; shift is ignored for
+ * BVG_TEXT_ASCII), on the calling thread's current device.  out == NULL or cap below the size: BVG_E_CAPACITY with *nbytes filled -- only
+ * the sizing pass is paid for, no text is written.  A negative successor, or an id the shift takes out of [0, 2^63 - 1]: BVG_E_ARG.
+ * One call formats fewer than 2^31 successors + nodes: writers go range by range (bvg_split_by_arcs) and append; the output does not
+ * depend on the ranges.  Device memory: 12 bytes per successor and per node of the range, the decoded range, and the text. */
+typedef struct bvg_text bvg_text;
+typedef struct bvg_text_error {             /* 24 bytes */
+    uint64_t byte;                          /* offset of the offending byte */
+    int64_t  line;                          /* 1-based: 1 + the line breaks before `byte` */
+    int32_t  reason;                        /* BVG_TEXT_BAD_BYTE ... */
+    int32_t  reserved;
+} bvg_text_error;
+enum { BVG_TEXT_BAD_BYTE = 1, BVG_TEXT_BAD_HEADER = 2, BVG_TEXT_TOO_LARGE = 3, BVG_TEXT_NOT_NODE = 4, BVG_TEXT_NOT_INCREASING = 5,
+       BVG_TEXT_SHIFT_RANGE = 6, BVG_TEXT_ARC_FIELDS = 7, BVG_TEXT_EOF = 8 };
+enum { BVG_TEXT_ASCII = 0, BVG_TEXT_ARCS = 1 };
+#define BVG_TEXT_SYMMETRIZE 1u
+#define BVG_TEXT_NO_LOOPS   2u
+int  bvg_text_parse_ascii(const void* text, uint64_t nbytes, int device, bvg_text** out, bvg_text_error* err);
+int  bvg_text_parse_ascii_dev(const void* d_text, uint64_t nbytes, int device, bvg_text** out, bvg_text_error* err);
+int  bvg_text_parse_arcs(const void* text, uint64_t nbytes, int64_t shift, uint32_t flags, int64_t min_nodes, int device, bvg_text** out, bvg_text_error* err);
+int  bvg_text_parse_arcs_dev(const void* d_text, uint64_t nbytes, int64_t shift, uint32_t flags, int64_t min_nodes, int device, bvg_text** out, bvg_text_error* err);
+void bvg_text_close(bvg_text* t);
+int  bvg_text_info(const bvg_text* t, int64_t* nodes, uint64_t* arcs);
+int  bvg_text_get(bvg_text* t, uint64_t* adj_off, uint64_t off_cap, int64_t* adj, uint64_t adj_cap);
+int  bvg_text_get_dev(bvg_text* t, void* d_adj_off, uint64_t off_cap, void* d_adj, uint64_t adj_cap);
+int  bvg_text_store(bvg_text* t, const bvg_params* p, int64_t chunk_nodes, uint8_t** graph, uint64_t* graph_bytes, uint64_t** offsets);
+int  bvg_text_format_ascii(bvg_graph* g, int64_t from, int64_t to, void* out, uint64_t cap, uint64_t* nbytes);
+int  bvg_text_format_ascii_dev(bvg_graph* g, int64_t from, int64_t to, void* d_out, uint64_t cap, uint64_t* nbytes);
+int  bvg_text_format_arcs(bvg_graph* g, int64_t from, int64_t to, int64_t shift, void* out, uint64_t cap, uint64_t* nbytes);
+int  bvg_text_format_arcs_dev(bvg_graph* g, int64_t from, int64_t to, int64_t shift, void* d_out, uint64_t cap, uint64_t* nbytes);
+int  bvg_text_format_csr(int kind, int64_t first_node, int64_t nodes, const uint64_t* adj_off, const int64_t* adj, int64_t shift,
+                         void* out, uint64_t cap, uint64_t* nbytes);
+
 /* ---- synthetic-workload helper (bench only): K back-to-back copies of the graph ----
  * BV records are translation invariant (every value is coded relative to the node id, Appendix A.3
  * of SURVEY.md), so the concatenation of K copies of the bit stream is a valid BVGraph with K*nodes

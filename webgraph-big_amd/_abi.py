@@ -131,6 +131,30 @@ def ef_signatures():
             "bvg_ef_store": [i64, i64, ci, ci, vp, vp, ci, pp, C.POINTER(u64), pp]}
 
 
+class TextError(C.Structure):
+    """bvg_text_error (24 bytes)."""
+    _fields_ = [("byte", C.c_uint64), ("line", C.c_int64), ("reason", C.c_int32), ("reserved", C.c_int32)]
+
+
+# bvg_text_error.reason (BVG_TEXT_BAD_BYTE ...), the `kind` of bvg_text_format_csr and the flags of bvg_text_parse_arcs
+TEXT_REASONS = {1: "bad_byte", 2: "bad_header", 3: "too_large", 4: "not_node", 5: "not_increasing", 6: "shift_range", 7: "arc_fields", 8: "eof"}
+TEXT_ASCII, TEXT_ARCS = 0, 1
+TEXT_SYMMETRIZE_FLAG, TEXT_NO_LOOPS_FLAG = 1, 2
+
+
+def text_signatures():
+    """argtypes of the bvg_text_* entry points (ASCIIGraph and arc lists, both ways), by name."""
+    vp, i64, u64, pp, ci, u32 = C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(C.c_void_p), C.c_int, C.c_uint32
+    E, N = C.POINTER(TextError), C.POINTER(C.c_uint64)
+    return {"bvg_text_parse_ascii": [vp, u64, ci, pp, E], "bvg_text_parse_ascii_dev": [vp, u64, ci, pp, E],
+            "bvg_text_parse_arcs": [vp, u64, i64, u32, i64, ci, pp, E], "bvg_text_parse_arcs_dev": [vp, u64, i64, u32, i64, ci, pp, E],
+            "bvg_text_close": [vp], "bvg_text_info": [vp, C.POINTER(i64), N], "bvg_text_get": [vp, vp, u64, vp, u64], "bvg_text_get_dev": [vp, vp, u64, vp, u64],
+            "bvg_text_store": [vp, C.POINTER(Params), i64, pp, N, pp],
+            "bvg_text_format_ascii": [vp, i64, i64, vp, u64, N], "bvg_text_format_ascii_dev": [vp, i64, i64, vp, u64, N],
+            "bvg_text_format_arcs": [vp, i64, i64, i64, vp, u64, N], "bvg_text_format_arcs_dev": [vp, i64, i64, i64, vp, u64, N],
+            "bvg_text_format_csr": [ci, i64, i64, vp, vp, i64, vp, u64, N]}
+
+
 OK, E_ARG, E_STATE, E_UNSUPPORTED, E_IO, E_EOF, E_NOMEM, E_HIP, E_CAPACITY = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 

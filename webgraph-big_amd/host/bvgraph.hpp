@@ -527,4 +527,75 @@ public:
     }
 };
 
+// ---- text graphs (ASCIIGraph.java, ArcListASCIIGraph.java) over bvg_text_*: a refusal carries the record of the first offending byte
+struct TextRefusal : std::runtime_error {
+    int status; bvg_text_error error;
+    TextRefusal(int st, const bvg_text_error& e, const std::string& what)
+        : std::runtime_error(what + ": reason " + std::to_string(e.reason) + " at line " + std::to_string(e.line) + ", byte " + std::to_string(e.byte)), status(st), error(e) {}
+};
+
+// a parsed text graph: its adjacency in CSR form, resident on the device
+class ParsedGraph {
+    bvg_text* t_; int64_t n_ = 0; uint64_t m_ = 0;
+public:
+    explicit ParsedGraph(bvg_text* t) : t_(t) {                              // owns t from here on: closed if the constructor fails
+        const int st = bvg_text_info(t_, &n_, &m_);
+        if (st != BVG_OK) { bvg_text_close(t_); check(st, "text_info"); }
+    }
+    ParsedGraph(const ParsedGraph&) = delete; ParsedGraph& operator=(const ParsedGraph&) = delete;
+    ~ParsedGraph() { bvg_text_close(t_); }
+    int64_t numNodes() const { return n_; }
+    int64_t numArcs() const { return (int64_t)m_; }
+    void csr(std::vector<uint64_t>& adjOff, std::vector<int64_t>& adj) const {
+        adjOff.resize((size_t)n_ + 1); adj.resize((size_t)m_);
+        check(bvg_text_get(t_, adjOff.data(), adjOff.size(), m_ ? adj.data() : nullptr, m_), "text_get");
+    }
+    // BVGraph.store of the resident CSR: the bytes of BVGraph::store on csr()
+    void store(const bvg_params& p, std::vector<uint8_t>& graph, std::vector<uint64_t>& offsets, int64_t chunkNodes = 0) const {
+        uint8_t* g = nullptr; uint64_t nb = 0; uint64_t* o = nullptr;
+        check(bvg_text_store(t_, &p, chunkNodes, &g, &nb, &o), "text_store");
+        graph.assign(g, g + nb); offsets.assign(o, o + n_ + 1);
+        bvg_free(g); bvg_free(o);
+    }
+};
+
+inline std::unique_ptr<ParsedGraph> finishParse(int st, bvg_text* t, const bvg_text_error& e, const char* what) {
+    if (st != BVG_OK && e.reason != 0) throw TextRefusal(st, e, what);
+    check(st, what);
+    return std::unique_ptr<ParsedGraph>(new ParsedGraph(t));
+}
+// ASCIIGraph.load on a text in memory: the node count, then one line of successors per node
+inline std::unique_ptr<ParsedGraph> loadASCIIGraph(const std::string& text, int device = 0) {
+    bvg_text* t = nullptr; bvg_text_error e{};
+    const int st = bvg_text_parse_ascii(text.data(), text.size(), device, &t, &e);
+    return finishParse(st, t, e, "loadASCIIGraph");
+}
+// ArcListASCIIGraph / ScatteredArcsASCIIGraph on a text in memory: `source TAB target` lines in any order
+inline std::unique_ptr<ParsedGraph> loadArcList(const std::string& text, int64_t shift = 0, bool symmetrize = false, bool noLoops = false, int64_t minNodes = 0, int device = 0) {
+    bvg_text* t = nullptr; bvg_text_error e{};
+    const int st = bvg_text_parse_arcs(text.data(), text.size(), shift, (symmetrize ? BVG_TEXT_SYMMETRIZE : 0u) | (noLoops ? BVG_TEXT_NO_LOOPS : 0u), minNodes, device, &t, &e);
+    return finishParse(st, t, e, "loadArcList");
+}
+// the lines of nodes [from, to) as ASCIIGraph.store writes them (never a header line), and their arcs as ArcListASCIIGraph.store writes them
+inline std::string formatASCIIGraph(BVGraph& g, int64_t from, int64_t to) {
+    uint64_t need = 0;
+    int st = bvg_text_format_ascii(g.handle(), from, to, nullptr, 0, &need);
+    if (st != BVG_E_CAPACITY) check(st, "formatASCIIGraph");
+    std::string body((size_t)need, '\0');
+    if (need) check(bvg_text_format_ascii(g.handle(), from, to, &body[0], need, &need), "formatASCIIGraph");
+    return body;
+}
+inline std::string formatArcList(BVGraph& g, int64_t from, int64_t to, int64_t shift = 0) {
+    uint64_t need = 0;
+    int st = bvg_text_format_arcs(g.handle(), from, to, shift, nullptr, 0, &need);
+    if (st != BVG_E_CAPACITY) check(st, "formatArcList");
+    std::string body((size_t)need, '\0');
+    if (need) check(bvg_text_format_arcs(g.handle(), from, to, shift, &body[0], need, &need), "formatArcList");
+    return body;
+}
+// ASCIIGraph.store / ArcListASCIIGraph.store of the whole graph into a string: the text of basename.graph-txt (the node count on a line of
+// its own, then every node's line), the text of the arc list
+inline std::string storeASCIIGraph(BVGraph& g) { return std::to_string(g.numNodes()) + "\n" + formatASCIIGraph(g, 0, g.numNodes()); }
+inline std::string storeArcList(BVGraph& g, int64_t shift = 0) { return formatArcList(g, 0, g.numNodes(), shift); }
+
 }  // namespace webgraph
