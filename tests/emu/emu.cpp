@@ -176,14 +176,25 @@ uint64_t clock() { static uint64_t c = 0; return c += 16; }
 // tests: the next `n` device allocations fail (hipErrorOutOfMemory), as on a card whose memory another handle holds
 static int g_fail_mallocs = 0;
 extern "C" void emu_fail_next_mallocs(int n) { g_fail_mallocs = n; }
+// ... or the k-th allocation from now on fails, once (k <= 0: none does); how many allocations were asked for so far, failed ones included,
+// and how many blocks are allocated at the moment (run_oom_sweep.py: no failure may leave a block behind once the handles are closed)
+static long g_fail_at = 0, g_malloc_count = 0, g_live_allocs = 0;
+extern "C" void emu_fail_malloc_at(long k) { g_fail_at = k > 0 ? g_malloc_count + k : 0; }
+extern "C" long emu_malloc_count() { return g_malloc_count; }
+extern "C" long emu_live_allocs() { return g_live_allocs; }
 hipError_t emu_malloc(void** p, size_t n) {
+    static std::mutex mu; std::lock_guard<std::mutex> lk(mu);      // (host threads of the library allocate side by side)
     *p = nullptr;
+    g_malloc_count++;
     if (g_fail_mallocs > 0) { g_fail_mallocs--; return hipErrorOutOfMemory; }
+    if (g_fail_at && g_malloc_count == g_fail_at) { g_fail_at = 0; return hipErrorOutOfMemory; }
     if (posix_memalign(p, 256, std::max<size_t>(n, 1)) != 0) { *p = nullptr; return hipErrorOutOfMemory; }
     memset(*p, 0xCD, n);                        // device memory is not zeroed
+    __atomic_add_fetch(&g_live_allocs, 1, __ATOMIC_RELAXED);
     return hipSuccess;
 }
-hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+static hipError_t emu_free(void* p) { if (p) __atomic_sub_fetch(&g_live_allocs, 1, __ATOMIC_RELAXED); free(p); return hipSuccess; }
+hipError_t hipFree(void* p) { return emu_free(p); }
+hipError_t hipHostFree(void* p) { return emu_free(p); }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); e->t = (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec; return hipSuccess; }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) { *ms = (float)((double)(b->t - a->t) * 1e-6); return hipSuccess; }

@@ -50,6 +50,17 @@ def test_a_failed_allocation_during_the_index_build_is_transient(emu_lib):
     assert out.stderr.count("warning: the residual skip index") == 1 and "out of device memory" in out.stderr, out.stderr[-2000:]
 
 
+def test_every_allocation_failing_in_turn_leaks_nothing(emu_lib):
+    """tests/emu/run_oom_sweep.py: open, two scans, decode_range, successors_batch, outdegrees, split_by_arcs, shard_bounds, a copy with another block size and
+    its scan, build_index, save_index / load_index, tile(2) and its scan, W.store, arc labels, the closes -- 117 device allocations -- run once per allocation
+    with that allocation failing.  Every call answers as the oracle does or raises MemoryError (BVG_E_NOMEM) and succeeds when repeated, and no device block
+    is left allocated once the handles are closed: the host code holds device memory in DevArray / DevWorkspace (csrc/bvg_host.h) alone.  Before that, 31 of
+    the 117 runs left up to five blocks behind (a handle whose second array could not be had, the block plan's arrays on every early return)."""
+    e = dict(os.environ); e.pop("BVG_HIP_LIB", None); e.pop("BVG_DEBUG", None); e.pop("BVG_EMU_LIB", None)
+    out = subprocess.run([sys.executable, os.path.join(EMU, "run_oom_sweep.py")], env=e, capture_output=True, text=True, timeout=1500)
+    assert out.returncode == 0 and "allocations 1..117, 0 failed" in out.stdout, out.stdout[-3000:] + out.stderr[-3000:]
+
+
 @pytest.mark.skipif(not os.environ.get("BVG_EMU_ASAN"), reason="opt-in (BVG_EMU_ASAN=1): the AddressSanitizer build of the emulated library takes ~4 minutes to compile")
 @pytest.mark.parametrize("flat", [0, 1])
 def test_kernels_under_address_sanitizer(flat):

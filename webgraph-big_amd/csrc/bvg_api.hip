@@ -13,16 +13,7 @@ namespace bvghost {
 // Per-handle device workspace for the materialising calls: grown on demand, kept between calls (a NodeIterator asks for batch
 // after batch of the same size; a fresh hipMalloc / hipFree pair per buffer and call cost more than the decode of a small batch).
 static int dr_ensure(bvg_graph* g, size_t bytes) {
-    if (bytes <= g->dr_ws_bytes) return 0;
-    if (g->dr_ws) { (void)hipFree(g->dr_ws); g->dr_ws = nullptr; g->dr_ws_bytes = 0; }
-    const size_t want = bytes + bytes / 4;
-    if (hipMalloc(&g->dr_ws, want) != hipSuccess) {
-        (void)hipGetLastError();
-        if (hipMalloc(&g->dr_ws, bytes) != hipSuccess) { (void)hipGetLastError(); g->dr_ws = nullptr; return BVG_E_NOMEM; }
-        g->dr_ws_bytes = bytes; return 0;
-    }
-    g->dr_ws_bytes = want;
-    return 0;
+    return bytes <= g->dr_ws.bytes() ? 0 : g->dr_ws.reserve(bytes + bytes / 4, bytes);   // (a quarter more than asked for, when that can be had)
 }
 
 int decode_range_impl(bvg_graph* g, int64_t from, int64_t to, int32_t* outdeg, int64_t* succ, uint64_t cap, uint64_t* n_succ, bool dev, bool narrow) {
@@ -38,7 +29,7 @@ int decode_range_impl(bvg_graph* g, int64_t from, int64_t to, int32_t* outdeg, i
     const size_t o_cum = 0, o_tmp = o_cum + al(((size_t)cnt + 1) * sizeof(uint64_t)), o_deg = o_tmp + al(scan_tmp_elems(cnt) * sizeof(uint64_t));
     const size_t o_succ = o_deg + al((size_t)cnt * sizeof(int32_t));
     int rc = dr_ensure(g, o_succ); if (rc) return rc;
-    auto at = [&](size_t off) { return (char*)g->dr_ws + off; };
+    auto at = [&](size_t off) { return g->dr_ws.at(off); };
     int32_t* d_deg = (dev && outdeg) ? outdeg : (int32_t*)at(o_deg);
     uint64_t* d_cum = (uint64_t*)at(o_cum);
     launch_outdegrees(sh->d_graph, sh->nbytes, sh->offs, from, to, sh->p.outdegree_coding, d_deg, nullptr, g->stream);
@@ -54,7 +45,7 @@ int decode_range_impl(bvg_graph* g, int64_t from, int64_t to, int32_t* outdeg, i
     int64_t* d_succ = succ;
     if (!dev) {
         const size_t per = sizeof(int64_t) + (narrow ? sizeof(uint32_t) : 0);
-        if (o_succ + (size_t)(total ? total : 1) * per + 256 > g->dr_ws_bytes) {
+        if (o_succ + (size_t)(total ? total : 1) * per + 256 > g->dr_ws.bytes()) {
             // growing moves the workspace: the prefix sums are recomputed rather than copied (two tiny kernels)
             rc = dr_ensure(g, o_succ + (size_t)(total ? total : 1) * per + 256); if (rc) return rc;
             d_deg = (int32_t*)at(o_deg); d_cum = (uint64_t*)at(o_cum);
@@ -148,20 +139,20 @@ static int bvg_successors_batch_impl(bvg_graph* g, const int64_t* nodes, int64_t
     std::vector<DeepRequest> deep;
     BatchBufs b{};
     auto prepare = [&]() -> int {
-        b = batch_bufs_at((char*)g->dr_ws + o_bufs, count);
-        HIPCHK(hipMemcpyAsync(g->dr_ws, nodes, c * sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
-        int r = batch_degrees(g, b, (const int64_t*)g->dr_ws, count, &total); if (r) return r;
-        return batch_halos(g, b, (const int64_t*)g->dr_ws, count, deep);
+        b = batch_bufs_at(g->dr_ws.at(o_bufs), count);
+        HIPCHK(hipMemcpyAsync(g->dr_ws.get(), nodes, c * sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
+        int r = batch_degrees(g, b, (const int64_t*)g->dr_ws.get(), count, &total); if (r) return r;
+        return batch_halos(g, b, (const int64_t*)g->dr_ws.get(), count, deep);
     };
     rc = prepare(); if (rc) return rc;
     if (n_succ) *n_succ = total;
     if (outdeg) HIPCHK(hipMemcpy(outdeg, b.deg, c * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (total > succ_cap || (!succ && total > 0)) return BVG_E_CAPACITY;
-    if (o_succ + (size_t)(total ? total : 1) * sizeof(int64_t) > g->dr_ws_bytes) {
+    if (o_succ + (size_t)(total ? total : 1) * sizeof(int64_t) > g->dr_ws.bytes()) {
         rc = dr_ensure(g, o_succ + (size_t)(total ? total : 1) * sizeof(int64_t)); if (rc) return rc;
         rc = prepare(); if (rc) return rc;                                   // the workspace moved: redo the (cheap) preparation in the new one
     }
-    int64_t* const d_succ = (int64_t*)((char*)g->dr_ws + o_succ);
+    int64_t* const d_succ = (int64_t*)g->dr_ws.at(o_succ);
     rc = batch_decode(g, b, count, d_succ);
     if (rc == 0 && total) {
         HIPCHK(hipMemcpyAsync(succ, d_succ, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
@@ -325,22 +316,9 @@ int bvg_copy(const bvg_graph* g, bvg_graph** out) {
 
 void bvg_close(bvg_graph* g) {
     if (!g) return;
-    (void)hipSetDevice(g->sh->device);
-    if (g->stream) { (void)hipStreamSynchronize(g->stream); (void)hipStreamDestroy(g->stream); }
-    if (g->ev0) (void)hipEventDestroy(g->ev0);
-    if (g->ev1) (void)hipEventDestroy(g->ev1);
-    if (g->tr_ws) (void)hipFree(g->tr_ws);
-    if (g->dr_ws) (void)hipFree(g->dr_ws);
-    if (g->flow_ws) (void)hipFree(g->flow_ws);
-    if (g->d_acc) (void)hipFree(g->d_acc);
-    if (g->d_fail) (void)hipFree(g->d_fail);
-    if (g->slow_ws) (void)hipFree(g->slow_ws);
-    if (g->giant_ws) (void)hipFree(g->giant_ws);
-    if (g->d_gslots) (void)hipFree(g->d_gslots);
-    for (auto& pd : g->pred2) if (pd.d_lists) (void)hipFree(pd.d_lists);
-    for (int i = 0; i < bvg_graph::kSide; i++) { if (g->side[i]) { (void)hipStreamSynchronize(g->side[i]); (void)hipStreamDestroy(g->side[i]); } if (g->side_ev[i]) (void)hipEventDestroy(g->side_ev[i]); }
-    release_shared(g->sh);
+    Shared* const sh = g->sh;
     delete g;
+    release_shared(sh);
 }
 
 int bvg_info(const bvg_graph* g, bvg_params* out) { if (!g || !out) return BVG_E_ARG; *out = g->sh->p; return 0; }
@@ -352,14 +330,14 @@ int bvg_get_offsets(bvg_graph* g, uint64_t* out) {
     HIPCHK(hipSetDevice(g->sh->device));
     const Shared* sh = g->sh; const int64_t n1 = sh->p.nodes + 1;
     if (!sh->offs.lo) { HIPCHK(hipMemcpy(out, sh->offs.wide, (size_t)n1 * sizeof(uint64_t), hipMemcpyDeviceToHost)); return 0; }
-    DevBuf tmp;                                                        // unpacked in pieces through a 128 MiB device buffer
+    DevArray<uint64_t> tmp;                                            // unpacked in pieces through a 128 MiB device buffer
     const int64_t step = (int64_t)1 << 24;
-    if (tmp.alloc((size_t)std::min<int64_t>(step, n1) * sizeof(uint64_t))) return BVG_E_NOMEM;
+    if (tmp.alloc((size_t)std::min<int64_t>(step, n1))) return BVG_E_NOMEM;
     for (int64_t first = 0; first < n1; first += step) {
         const int64_t cnt = std::min<int64_t>(step, n1 - first);
-        launch_unpack_offsets(sh->offs, first, cnt, (uint64_t*)tmp.p, g->stream);
+        launch_unpack_offsets(sh->offs, first, cnt, tmp, g->stream);
         HIPCHK(hipStreamSynchronize(g->stream));
-        HIPCHK(hipMemcpy(out + first, tmp.p, (size_t)cnt * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out + first, tmp, (size_t)cnt * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
     return 0;
 }
@@ -369,12 +347,11 @@ int bvg_outdegrees(bvg_graph* g, int64_t from, int64_t to, int32_t* out) {
     if (from < 0 || to > g->sh->p.nodes || from > to) return BVG_E_ARG;            // BVG:823
     if (from == to) return 0;
     HIPCHK(hipSetDevice(g->sh->device));
-    int32_t* d = nullptr;
-    HIPCHK(hipMalloc(&d, (size_t)(to - from) * sizeof(int32_t)));
+    DevArray<int32_t> d;
+    if (d.alloc((size_t)(to - from))) return BVG_E_NOMEM;
     launch_outdegrees(g->sh->d_graph, g->sh->nbytes, g->sh->offs, from, to, g->sh->p.outdegree_coding, d, nullptr, g->stream);
     hipError_t e = hipMemcpyAsync(out, d, (size_t)(to - from) * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    (void)hipFree(d);
     return e == hipSuccess ? 0 : BVG_E_HIP;
 }
 
@@ -427,15 +404,8 @@ static int transpose_impl(bvg_graph* g, uint64_t* toffsets, int64_t* tsucc, uint
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_deg = 0, o_cum = o_deg + al(nn * sizeof(int32_t)), o_tmp = o_cum + al((nn + 1) * sizeof(uint64_t));
     const size_t o_bad = o_tmp + al(scan_tmp_elems((int64_t)nn) * sizeof(uint64_t)), o_arcs = o_bad + 256;
-    auto ensure = [&](size_t bytes) -> int {
-        if (bytes <= g->tr_ws_bytes) return 0;
-        if (g->tr_ws) { (void)hipFree(g->tr_ws); g->tr_ws = nullptr; g->tr_ws_bytes = 0; }
-        if (hipMalloc(&g->tr_ws, bytes) != hipSuccess) { (void)hipGetLastError(); return BVG_E_NOMEM; }
-        g->tr_ws_bytes = bytes;
-        return 0;
-    };
-    int rc = ensure(o_arcs); if (rc) return rc;
-    auto at = [&](size_t off) { return (char*)g->tr_ws + off; };
+    int rc = g->tr_ws.reserve(o_arcs); if (rc) return rc;
+    auto at = [&](size_t off) { return g->tr_ws.at(off); };
     HIPCHK(hipMemsetAsync(at(o_bad), 0, sizeof(unsigned), g->stream));
     HIPCHK(hipMemsetAsync(at(o_cum), 0, (nn + 1) * sizeof(uint64_t), g->stream));
     uint64_t total = 0;
@@ -452,11 +422,11 @@ static int transpose_impl(bvg_graph* g, uint64_t* toffsets, int64_t* tsucc, uint
     const size_t o_succ = o_arcs, o_src = o_succ + al(mm * 8), o_keys = o_src + al(mm * 8), o_temp = o_keys + al(mm * 8);
     const size_t o_toff = o_temp + al(temp_b ? temp_b : 16), o_ts = o_toff + (dev ? 0 : al((nn + 1) * 8)), o_end = o_ts + (dev ? 0 : al(mm * 8));
     {   // growing the workspace must not lose the prefix sums: save them on the host side of the copy only when it really grows
-        if (o_end > g->tr_ws_bytes) {
+        if (o_end > g->tr_ws.bytes()) {
             std::vector<char> keep(o_arcs);
-            HIPCHK(hipMemcpy(keep.data(), g->tr_ws, o_arcs, hipMemcpyDeviceToHost));
-            rc = ensure(o_end); if (rc) return rc;
-            HIPCHK(hipMemcpy(g->tr_ws, keep.data(), o_arcs, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(keep.data(), g->tr_ws.get(), o_arcs, hipMemcpyDeviceToHost));
+            rc = g->tr_ws.reserve(o_end); if (rc) return rc;
+            HIPCHK(hipMemcpy(g->tr_ws.get(), keep.data(), o_arcs, hipMemcpyHostToDevice));
         }
     }
     uint64_t* const d_cum = (uint64_t*)at(o_cum); int64_t* const d_succ = (int64_t*)at(o_succ);
@@ -492,34 +462,33 @@ static int symmetrize_impl(bvg_graph* g, uint64_t* soffsets, int64_t* ssucc, uin
     const int64_t n = sh->p.nodes;
     HIPCHK(hipSetDevice(sh->device));
     uint64_t arcs = 0;
-    uint64_t* d_toff = nullptr; int64_t* d_ts = nullptr; int32_t* d_cnt = nullptr; uint64_t* d_soff = nullptr; uint64_t* d_tmp = nullptr; int64_t* d_out = nullptr;
-    auto done = [&](int code) { for (void* p : {(void*)d_toff, (void*)d_ts, (void*)d_cnt, (void*)d_soff, (void*)d_tmp, (void*)d_out}) if (p) (void)hipFree(p); return code; };
+    DevArray<uint64_t> d_toff, d_soff, d_tmp; DevArray<int64_t> d_ts, d_out; DevArray<int32_t> d_cnt;
     const size_t nn = (size_t)(n > 0 ? n : 1);
-    if (hipMalloc(&d_toff, (nn + 1) * 8) != hipSuccess) return done(BVG_E_NOMEM);
+    if (d_toff.alloc(nn + 1)) return BVG_E_NOMEM;
     int r = transpose_impl(g, d_toff, nullptr, 0, &arcs, true);                // arc count (sum of the outdegrees)
-    if (r && r != BVG_E_CAPACITY) return done(r);
-    if (hipMalloc(&d_ts, (size_t)(arcs ? arcs : 1) * 8) != hipSuccess) return done(BVG_E_NOMEM);
-    r = transpose_impl(g, d_toff, d_ts, arcs, &arcs, true); if (r) return done(r);
-    const uint64_t* d_cum = (const uint64_t*)((char*)g->tr_ws + g->tr_o_cum); const int64_t* d_succ = (const int64_t*)((char*)g->tr_ws + g->tr_o_succ);
-    if (hipMalloc(&d_cnt, nn * 4) != hipSuccess || hipMalloc(&d_soff, (nn + 1) * 8) != hipSuccess || hipMalloc(&d_tmp, scan_tmp_elems((int64_t)nn) * 8) != hipSuccess) return done(BVG_E_NOMEM);
-    if (hipMemsetAsync(d_soff, 0, (nn + 1) * 8, g->stream) != hipSuccess) return done(BVG_E_HIP);
+    if (r && r != BVG_E_CAPACITY) return r;
+    if (d_ts.alloc((size_t)arcs)) return BVG_E_NOMEM;
+    r = transpose_impl(g, d_toff, d_ts, arcs, &arcs, true); if (r) return r;
+    const uint64_t* d_cum = (const uint64_t*)g->tr_ws.at(g->tr_o_cum); const int64_t* d_succ = (const int64_t*)g->tr_ws.at(g->tr_o_succ);
+    if (d_cnt.alloc(nn) || d_soff.alloc(nn + 1) || d_tmp.alloc(scan_tmp_elems((int64_t)nn))) return BVG_E_NOMEM;
+    if (hipMemsetAsync(d_soff, 0, (nn + 1) * 8, g->stream) != hipSuccess) return BVG_E_HIP;
     uint64_t total = 0;
     if (n > 0) {
         launch_union_count(d_cum, d_succ, d_toff, d_ts, n, d_cnt, g->stream);
         launch_exclusive_scan(d_cnt, d_soff, n, d_tmp, g->stream);
-        if (hipMemcpyAsync(&total, d_soff + n, 8, hipMemcpyDeviceToHost, g->stream) != hipSuccess) return done(BVG_E_HIP);
+        if (hipMemcpyAsync(&total, d_soff + n, 8, hipMemcpyDeviceToHost, g->stream) != hipSuccess) return BVG_E_HIP;
     }
-    if (hipStreamSynchronize(g->stream) != hipSuccess) return done(BVG_E_HIP);
+    if (hipStreamSynchronize(g->stream) != hipSuccess) return BVG_E_HIP;
     if (n_arcs) *n_arcs = total;
-    if (dev) { if (hipMemcpyAsync(soffsets, d_soff, (size_t)(n + 1) * 8, hipMemcpyDeviceToDevice, g->stream) != hipSuccess) return done(BVG_E_HIP); }
-    else if (hipMemcpy(soffsets, d_soff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) return done(BVG_E_HIP);
-    if (total > cap || (!ssucc && total > 0)) { (void)hipStreamSynchronize(g->stream); return done(BVG_E_CAPACITY); }
+    if (dev) { if (hipMemcpyAsync(soffsets, d_soff, (size_t)(n + 1) * 8, hipMemcpyDeviceToDevice, g->stream) != hipSuccess) return BVG_E_HIP; }
+    else if (hipMemcpy(soffsets, d_soff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) return BVG_E_HIP;
+    if (total > cap || (!ssucc && total > 0)) { (void)hipStreamSynchronize(g->stream); return BVG_E_CAPACITY; }
     int64_t* d_dst = ssucc;
-    if (!dev) { if (hipMalloc(&d_out, (size_t)(total ? total : 1) * 8) != hipSuccess) return done(BVG_E_NOMEM); d_dst = d_out; }
+    if (!dev) { if (d_out.alloc((size_t)total)) return BVG_E_NOMEM; d_dst = d_out; }
     launch_union_write(d_cum, d_succ, d_toff, d_ts, n, d_soff, d_dst, g->stream);
-    if (!dev && total && hipMemcpyAsync(ssucc, d_out, (size_t)total * 8, hipMemcpyDeviceToHost, g->stream) != hipSuccess) return done(BVG_E_HIP);
-    if (hipStreamSynchronize(g->stream) != hipSuccess) return done(BVG_E_HIP);
-    return done(0);
+    if (!dev && total && hipMemcpyAsync(ssucc, d_out, (size_t)total * 8, hipMemcpyDeviceToHost, g->stream) != hipSuccess) return BVG_E_HIP;
+    if (hipStreamSynchronize(g->stream) != hipSuccess) return BVG_E_HIP;
+    return 0;
 }
 
 int bvg_symmetrize(bvg_graph* g, uint64_t* soffsets, int64_t* ssucc, uint64_t ssucc_cap, uint64_t* n_arcs) {
@@ -544,21 +513,19 @@ static int bvg_split_by_arcs_impl(bvg_graph* g, int k, int64_t* bounds) {
     HIPCHK(hipSetDevice(sh->device));
     const int64_t n = sh->p.nodes;
     if (n == 0) { for (int i = 0; i <= k; i++) bounds[i] = 0; return 0; }
-    int32_t* d_deg = nullptr; uint64_t* d_cum = nullptr; uint64_t* d_tmp = nullptr; uint64_t* d_first = nullptr;
-    auto done = [&](int code) { for (void* p : {(void*)d_deg, (void*)d_cum, (void*)d_tmp, (void*)d_first}) if (p) (void)hipFree(p); return code; };
-    if (hipMalloc(&d_deg, (size_t)n * 4) != hipSuccess || hipMalloc(&d_cum, (size_t)(n + 1) * 8) != hipSuccess ||
-        hipMalloc(&d_tmp, scan_tmp_elems(n) * 8) != hipSuccess || hipMalloc(&d_first, ((size_t)k + 1) * 8) != hipSuccess) return done(BVG_E_NOMEM);
+    DevArray<int32_t> d_deg; DevArray<uint64_t> d_cum, d_tmp, d_first;
+    if (d_deg.alloc((size_t)n) || d_cum.alloc((size_t)n + 1) || d_tmp.alloc(scan_tmp_elems(n)) || d_first.alloc((size_t)k + 1)) return BVG_E_NOMEM;
     launch_outdegrees(sh->d_graph, sh->nbytes, sh->offs, 0, n, sh->p.outdegree_coding, d_deg, nullptr, g->stream);
     launch_exclusive_scan(d_deg, d_cum, n, d_tmp, g->stream);
     uint64_t arcs = 0;
-    if (hipMemcpyAsync(&arcs, d_cum + n, 8, hipMemcpyDeviceToHost, g->stream) != hipSuccess || hipStreamSynchronize(g->stream) != hipSuccess) return done(BVG_E_HIP);
+    if (hipMemcpyAsync(&arcs, d_cum + n, 8, hipMemcpyDeviceToHost, g->stream) != hipSuccess || hipStreamSynchronize(g->stream) != hipSuccess) return BVG_E_HIP;
     uint64_t per = (arcs + (uint64_t)k - 1) / (uint64_t)k; if (per == 0) per = 1;
     launch_plan_boundaries(Offsets{nullptr, nullptr, d_cum}, n, per, (uint64_t)k, d_first, g->stream);   // (cumulative outdegrees: a plain array)
     std::vector<uint64_t> f((size_t)k + 1);
-    if (hipMemcpyAsync(f.data(), d_first, ((size_t)k + 1) * 8, hipMemcpyDeviceToHost, g->stream) != hipSuccess || hipStreamSynchronize(g->stream) != hipSuccess) return done(BVG_E_HIP);
+    if (hipMemcpyAsync(f.data(), d_first, ((size_t)k + 1) * 8, hipMemcpyDeviceToHost, g->stream) != hipSuccess || hipStreamSynchronize(g->stream) != hipSuccess) return BVG_E_HIP;
     for (int i = 0; i <= k; i++) bounds[i] = (int64_t)f[(size_t)i];
     bounds[0] = 0; bounds[k] = n;
-    return done(0);
+    return 0;
 }
 
 static int bvg_split_by_bits_impl(bvg_graph* g, int k, int64_t* bounds) {
@@ -568,13 +535,12 @@ static int bvg_split_by_bits_impl(bvg_graph* g, int k, int64_t* bounds) {
     const int64_t n = sh->p.nodes;
     if (n == 0) { for (int i = 0; i <= k; i++) bounds[i] = 0; return 0; }
     uint64_t per = (sh->total_bits + (uint64_t)k - 1) / (uint64_t)k; if (per == 0) per = 1;
-    uint64_t* d_first = nullptr;
-    HIPCHK(hipMalloc(&d_first, ((size_t)k + 1) * sizeof(uint64_t)));
+    DevArray<uint64_t> d_first;
+    if (d_first.alloc((size_t)k + 1)) return BVG_E_NOMEM;
     launch_plan_boundaries(sh->offs, n, per, (uint64_t)k, d_first, g->stream);
     std::vector<uint64_t> f((size_t)k + 1);
     hipError_t e = hipMemcpyAsync(f.data(), d_first, ((size_t)k + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    (void)hipFree(d_first);
     if (e != hipSuccess) return BVG_E_HIP;
     for (int i = 0; i <= k; i++) bounds[i] = (int64_t)f[(size_t)i];
     bounds[0] = 0; bounds[k] = n;
@@ -696,25 +662,21 @@ static int bvg_mosaic_impl(const bvg_graph* const* bases, int k, int64_t cycles,
     const uint64_t nbytes = (total_bits + 7) / 8;
     const uint64_t padded = ((nbytes + 15) & ~15ull) + kPad;
     const int64_t n = m.cycle_nodes * cycles;
-    uint8_t* d_graph = nullptr; uint32_t* d_lo = nullptr; uint64_t* d_hi = nullptr;
+    DevArray<uint8_t> d_graph; PackedOffsets pk;
     const size_t n1 = (size_t)n + 1;
-    DevBuf flag;
-    if (flag.alloc(sizeof(unsigned)) || hipMemset(flag.p, 0, sizeof(unsigned)) != hipSuccess) return BVG_E_NOMEM;
-    HIPCHK(hipMalloc(&d_graph, padded));
-    if (hipMalloc(&d_lo, n1 * sizeof(uint32_t)) != hipSuccess || hipMalloc(&d_hi, ((n1 >> kOffShift) + 2) * sizeof(uint64_t)) != hipSuccess) {
-        (void)hipFree(d_graph); if (d_lo) (void)hipFree(d_lo); return BVG_E_NOMEM;
-    }
+    DevArray<unsigned> flag;
+    if (flag.alloc(1) || hipMemset(flag, 0, sizeof(unsigned)) != hipSuccess) return BVG_E_NOMEM;
+    if (d_graph.alloc(padded) || pk.lo.alloc(n1) || pk.hi.alloc((n1 >> kOffShift) + 2)) return BVG_E_NOMEM;
     hipStream_t st = bases[0]->stream;
     launch_mosaic_graph(m, d_graph, padded, cycles, st);
-    launch_mosaic_offsets(m, cycles, d_lo, d_hi, (unsigned*)flag.p, st);
+    launch_mosaic_offsets(m, cycles, pk.lo, pk.hi, flag, st);
     unsigned over = 0;
-    if (hipMemcpyAsync(&over, flag.p, sizeof over, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) over = 2;
-    if (over) { (void)hipFree(d_graph); (void)hipFree(d_lo); (void)hipFree(d_hi); return over == 2 ? BVG_E_HIP : BVG_E_UNSUPPORTED; }   // a group of 2^kOffShift records spans 2^32 bits: not packable
+    if (hipMemcpyAsync(&over, flag, sizeof over, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) over = 2;
+    if (over) return over == 2 ? BVG_E_HIP : BVG_E_UNSUPPORTED;       // a group of 2^kOffShift records spans 2^32 bits: not packable
     bvg_params p = b0->p; p.nodes = n; p.arcs = arcs < 0 ? -1 : arcs * cycles;
-    const PackedOffsets pk{d_lo, d_hi};
     int r = open_common(&p, nullptr, d_graph, nbytes, nullptr, nullptr, b0->device, out, &pk);
-    if (r) { (void)hipFree(d_graph); return r; }                      // (open_common owns the index from the start)
-    (*out)->sh->own_graph = true;
+    if (r) return r;
+    (*out)->sh->own_graph.adopt(d_graph.release(), padded);          // (the new handle read it as a caller's array so far)
     (*out)->tun = bases[0]->tun;
     return 0;
 }
@@ -747,20 +709,20 @@ int bvg_store(const bvg_params* p, int64_t nodes, const uint64_t* adj_off, const
         r = ensure_device(device); if (r) return r;
         const uint64_t m = adj_off[nodes];
         if (m && !adj) return BVG_E_ARG;
-        uint64_t* d_off = nullptr; int64_t* d_adj = nullptr; uint8_t* d_graph = nullptr; uint64_t* d_offsets = nullptr;
-        auto done = [&](int code) { for (void* x : {(void*)d_off, (void*)d_adj, (void*)d_graph, (void*)d_offsets}) if (x) (void)hipFree(x); return code; };
-        if (hipMalloc(&d_off, ((size_t)nodes + 1) * sizeof(uint64_t)) != hipSuccess || hipMalloc(&d_adj, (size_t)(m ? m : 1) * sizeof(int64_t)) != hipSuccess) { (void)hipGetLastError(); return done(BVG_E_NOMEM); }
-        if (hipMemcpy(d_off, adj_off, ((size_t)nodes + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) return done(BVG_E_HIP);
-        if (m && hipMemcpy(d_adj, adj, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) return done(BVG_E_HIP);
-        uint64_t nbytes = 0;
-        r = encode_store_dev(q, d_off, d_adj, nodes, chunk_nodes, nullptr, &d_graph, &nbytes, &d_offsets);
-        if (r) return done(r);
-        uint8_t* hg = (uint8_t*)calloc((size_t)nbytes + 16, 1); uint64_t* ho = (uint64_t*)malloc(((size_t)nodes + 1) * sizeof(uint64_t));
-        if (!hg || !ho) { free(hg); free(ho); return done(BVG_E_NOMEM); }
-        if ((nbytes && hipMemcpy(hg, d_graph, (size_t)nbytes, hipMemcpyDeviceToHost) != hipSuccess) ||
-            hipMemcpy(ho, d_offsets, ((size_t)nodes + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) { free(hg); free(ho); return done(BVG_E_HIP); }
-        *graph = hg; *graph_bytes = nbytes; *offsets = ho;
-        return done(0);
+        DevArray<uint64_t> d_off, d_offsets; DevArray<int64_t> d_adj; DevArray<uint8_t> d_graph;
+        if (d_off.alloc((size_t)nodes + 1) || d_adj.alloc((size_t)m)) return BVG_E_NOMEM;
+        if (hipMemcpy(d_off, adj_off, ((size_t)nodes + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) return BVG_E_HIP;
+        if (m && hipMemcpy(d_adj, adj, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) return BVG_E_HIP;
+        uint64_t nbytes = 0; uint8_t* pg = nullptr; uint64_t* po = nullptr;
+        r = encode_store_dev(q, d_off, d_adj, nodes, chunk_nodes, nullptr, &pg, &nbytes, &po);
+        if (r) return r;
+        d_graph.adopt(pg, (size_t)nbytes); d_offsets.adopt(po, (size_t)nodes + 1);
+        HostArray<uint8_t> hg((uint8_t*)calloc((size_t)nbytes + 16, 1)); HostArray<uint64_t> ho((uint64_t*)malloc(((size_t)nodes + 1) * sizeof(uint64_t)));
+        if (!hg || !ho) return BVG_E_NOMEM;
+        if ((nbytes && hipMemcpy(hg.get(), d_graph, (size_t)nbytes, hipMemcpyDeviceToHost) != hipSuccess) ||
+            hipMemcpy(ho.get(), d_offsets, ((size_t)nodes + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return BVG_E_HIP;
+        *graph = hg.release(); *graph_bytes = nbytes; *offsets = ho.release();
+        return 0;
     });
 }
 void bvg_free(void* p) { free(p); }

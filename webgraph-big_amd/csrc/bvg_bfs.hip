@@ -165,27 +165,18 @@ struct InLevel {
 using bvghost::Batch;
 using bvghost::BatchBufs;
 using bvghost::DeepRequest;
-using bvghost::DevBuf;
 
 namespace {
 
 constexpr uint64_t kMaxBudgetArcs = 1ull << 30;    // 8 GiB of successors per batch.  Below kMaxBatchArcs: the object keeps two such buffers between visits (succ for the
-                                                   // frontier route, sw_ws for the sweep), each with Grow's quarter of slack
+                                                   // frontier route, sw_ws for the sweep), each with grow()'s quarter of slack
 constexpr uint64_t kSmallCap = 1ull << 16;         // winners up to this many are sorted; more: the node range is compacted
 constexpr int64_t kPiece = 1ll << 24;              // requests of one frontier piece (its node-side arrays: ~100 bytes each)
 constexpr int64_t kChunk = 1ll << 20;              // nodes of one visit_all search chunk
 constexpr uint64_t kSwitchDen = 16;                // sweep when the frontier's outdegrees sum to >= arcs / 16 (UNMEASURED default: DESIGN.md 7c)
 
-struct Grow {                                      // a device buffer grown on demand, contents not kept
-    DevBuf b; size_t bytes = 0;
-    int ensure(size_t want) {
-        if (want <= bytes) return 0;
-        if (b.p) { (void)hipFree(b.release()); bytes = 0; }
-        if (b.alloc(want + want / 4)) return BVG_E_NOMEM;
-        bytes = want + want / 4;
-        return 0;
-    }
-};
+// a workspace of the object grown on demand, with a quarter of slack; contents not kept
+int grow(DevWorkspace& w, size_t want) { return want <= w.bytes() ? 0 : w.reserve(want + want / 4); }
 
 }  // namespace
 
@@ -193,7 +184,8 @@ struct bvg_bfs {
     bvg_graph* g = nullptr;                        // a bvg_copy() flyweight: own stream and workspaces
     bool parent = false, wide = false;
     int64_t n = 0;
-    DevBuf marker, cand, dist, queue, ctl, small;
+    DevArray<uint8_t> marker, cand;                // uint32 per node, uint64 when `wide`
+    DevArray<int32_t> dist; DevArray<int64_t> queue, small; DevArray<unsigned long long> ctl;
     std::vector<uint64_t> cuts;
     int64_t round = -1; uint64_t qsize = 0;
     // knobs
@@ -201,7 +193,7 @@ struct bvg_bfs {
     uint64_t per = 0, small_cap = kSmallCap, switch_den = kSwitchDen;
     // the graph in arc-bounded node ranges (sweep route), planned at the first need
     bool planned = false; bvghost::SweepPlan sweep; uint64_t arcs = 0; bool arcs_known = false;
-    Grow fr_bufs, succ, sw_ws, prim, chunk_ws, wide_out;
+    DevWorkspace fr_bufs, succ, sw_ws, prim, chunk_ws, wide_out;
     // visit_all's chunk
     int64_t ch_a = -1, ch_b = -1;
     uint64_t counters[BVG_BFS_COUNTERS] = {};
@@ -214,7 +206,7 @@ enum : int { kFrontierLevels, kSweepLevels, kDeep, kFrontierBatches, kSweepBatch
 
 template <typename T> int clear_t(bvg_bfs* v) {
     bvg_graph* g = v->g;
-    if (v->n) hipLaunchKernelGGL((bfs_fill_kernel<T>), dim3(grid(v->n, 256)), dim3(256), 0, g->stream, (T*)v->marker.p, (T*)v->cand.p, (int32_t*)v->dist.p, v->n);
+    if (v->n) hipLaunchKernelGGL((bfs_fill_kernel<T>), dim3(grid(v->n, 256)), dim3(256), 0, g->stream, (T*)v->marker.get(), (T*)v->cand.get(), v->dist.get(), v->n);
     v->round = -1; v->qsize = 0; v->cuts.clear();
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(g->stream));
@@ -236,8 +228,8 @@ int ensure_plan(bvg_bfs* v) {
 template <typename T> void launch_mark(bvg_bfs* v, bool sweep, const uint64_t* cum, const int64_t* nodes, int64_t lo, int64_t cnt, const int64_t* succ, int32_t d) {
     bvg_graph* g = v->g;
     const dim3 gr(grid(cnt, 256)), bl(256);
-    T* const marker = (T*)v->marker.p; T* const cand = (T*)v->cand.p; int32_t* const dist = (int32_t*)v->dist.p;
-    unsigned long long* const ctl = (unsigned long long*)v->ctl.p; int64_t* const small = (int64_t*)v->small.p;
+    T* const marker = (T*)v->marker.get(); T* const cand = (T*)v->cand.get(); int32_t* const dist = v->dist.get();
+    unsigned long long* const ctl = v->ctl.get(); int64_t* const small = v->small.get();
     const T round = (T)v->round;
 #define BFS_MARK(P, S) hipLaunchKernelGGL((bfs_mark_kernel<T, P, S>), gr, bl, 0, g->stream, cum, nodes, lo, cnt, succ, v->n, marker, cand, dist, d, round, ctl, small, v->small_cap)
     if (v->parent) { if (sweep) BFS_MARK(true, true); else BFS_MARK(true, false); }
@@ -250,8 +242,8 @@ int decode_requests(bvg_bfs* v, const BatchBufs& b, const int64_t* d_nodes, int6
     bvg_graph* g = v->g;
     std::vector<DeepRequest> deep;
     int rc = batch_halos(g, b, d_nodes, count, deep); if (rc) return rc;
-    rc = v->succ.ensure((size_t)(total ? total : 1) * 8); if (rc) return rc;
-    int64_t* const d_succ = (int64_t*)v->succ.b.p;
+    rc = grow(v->succ, (size_t)(total ? total : 1) * 8); if (rc) return rc;
+    int64_t* const d_succ = (int64_t*)v->succ.get();
     rc = batch_decode(g, b, count, d_succ); if (rc) return rc;
     for (const DeepRequest& q : deep) {                                     // through the block plan, one by one (few)
         int64_t x = 0; uint64_t got = 0;
@@ -269,13 +261,13 @@ int decode_requests(bvg_bfs* v, const BatchBufs& b, const int64_t* d_nodes, int6
 // marked so far stays (marking is idempotent: a node is won once).
 template <typename T> int expand_frontier(bvg_bfs* v, uint64_t lo, uint64_t hi, int32_t d, bool autoroute, bool* switched) {
     bvg_graph* g = v->g;
-    const int64_t* const q = (const int64_t*)v->queue.p;
+    const int64_t* const q = v->queue.get();
     uint64_t level_arcs = 0;
     *switched = false;
     for (uint64_t p0 = lo; p0 < hi; p0 += (uint64_t)kPiece) {
         const int64_t cnt = (int64_t)std::min<uint64_t>(hi - p0, (uint64_t)kPiece);
-        int rc = v->fr_bufs.ensure(batch_bufs_bytes(cnt)); if (rc) return rc;
-        BatchBufs b = batch_bufs_at((char*)v->fr_bufs.b.p, cnt);
+        int rc = grow(v->fr_bufs, batch_bufs_bytes(cnt)); if (rc) return rc;
+        BatchBufs b = batch_bufs_at(v->fr_bufs.at(0), cnt);
         uint64_t total = 0;
         rc = batch_degrees(g, b, q + p0, cnt, &total); if (rc) return rc;
         level_arcs += total;
@@ -283,7 +275,7 @@ template <typename T> int expand_frontier(bvg_bfs* v, uint64_t lo, uint64_t hi, 
         if (!total) continue;
         if (total <= v->per) {
             rc = decode_requests(v, b, q + p0, cnt, total); if (rc) return rc;
-            launch_mark<T>(v, false, b.cum, q + p0, 0, cnt, (const int64_t*)v->succ.b.p, d);
+            launch_mark<T>(v, false, b.cum, q + p0, 0, cnt, (const int64_t*)v->succ.get(), d);
             v->counters[kFrontierBatches]++;
             continue;
         }
@@ -291,11 +283,11 @@ template <typename T> int expand_frontier(bvg_bfs* v, uint64_t lo, uint64_t hi, 
         rc = cut_batches(g, b.cum, cnt, total, v->per, parts, &longest); if (rc) return rc;
         for (const Batch& pt : parts) {
             const int64_t c = pt.hi - pt.lo;
-            b = batch_bufs_at((char*)v->fr_bufs.b.p, c);
+            b = batch_bufs_at(v->fr_bufs.at(0), c);
             rc = batch_degrees(g, b, q + p0 + pt.lo, c, &total); if (rc) return rc;
             if (!total) continue;
             rc = decode_requests(v, b, q + p0 + pt.lo, c, total); if (rc) return rc;
-            launch_mark<T>(v, false, b.cum, q + p0 + pt.lo, 0, c, (const int64_t*)v->succ.b.p, d);
+            launch_mark<T>(v, false, b.cum, q + p0 + pt.lo, 0, c, (const int64_t*)v->succ.get(), d);
             v->counters[kFrontierBatches]++;
         }
     }
@@ -307,8 +299,8 @@ template <typename T> int expand_sweep(bvg_bfs* v, int32_t d) {
     int rc = ensure_plan(v); if (rc) return rc;
     bvghost::SweepPlan& sp = v->sweep;
     if (sp.batches.empty()) return 0;
-    rc = v->sw_ws.ensure(sp.bytes); if (rc) return rc;
-    sp.bind(v->sw_ws.b.p);
+    rc = grow(v->sw_ws, sp.bytes); if (rc) return rc;
+    sp.bind(v->sw_ws.get());
     for (const Batch& b : sp.batches) {
         rc = sp.decode(g, b); if (rc) return rc;
         launch_mark<T>(v, true, sp.cum(), nullptr, b.lo, b.hi - b.lo, sp.succ(), d);
@@ -321,20 +313,20 @@ template <typename T> int expand_sweep(bvg_bfs* v, int32_t d) {
 // the winners of level d + 1 into queue[at, at + added), in increasing id
 template <typename T> int next_level(bvg_bfs* v, uint64_t at, uint64_t added, int32_t d) {
     bvg_graph* g = v->g;
-    int64_t* const out = (int64_t*)v->queue.p + at;
+    int64_t* const out = v->queue.get() + at;
     if (added <= v->small_cap) {
-        if (added == 1) HIPCHK(hipMemcpyAsync(out, v->small.p, 8, hipMemcpyDeviceToDevice, g->stream));
+        if (added == 1) HIPCHK(hipMemcpyAsync(out, v->small.get(), 8, hipMemcpyDeviceToDevice, g->stream));
         else {
             const unsigned bits = 64u - (unsigned)__builtin_clzll((unsigned long long)(v->n > 1 ? v->n - 1 : 1));
             size_t tb = 0;
             if (rocprim::radix_sort_keys(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)added, 0u, bits, g->stream) != hipSuccess) return BVG_E_HIP;
-            int rc = v->prim.ensure(tb ? tb : 1); if (rc) return rc;
-            if (rocprim::radix_sort_keys(v->prim.b.p, tb, (const uint64_t*)v->small.p, (uint64_t*)out, (size_t)added, 0u, bits, g->stream) != hipSuccess) return BVG_E_HIP;
+            int rc = grow(v->prim, tb ? tb : 1); if (rc) return rc;
+            if (rocprim::radix_sort_keys(v->prim.get(), tb, (const uint64_t*)v->small.get(), (uint64_t*)out, (size_t)added, 0u, bits, g->stream) != hipSuccess) return BVG_E_HIP;
         }
         v->counters[kSortedLevels]++;
     } else {
-        const InLevel pred{(const int32_t*)v->dist.p, d + 1};
-        unsigned long long* const d_sel = (unsigned long long*)v->ctl.p + kCtlFirst;   // (what a call selected)
+        const InLevel pred{v->dist.get(), d + 1};
+        unsigned long long* const d_sel = v->ctl.get() + kCtlFirst;   // (what a call selected)
         const bool ranges = v->n > bvghost::kMaxBatchNodes;                  // node ranges below 2^32 elements per call; their outputs follow one another
         uint64_t done = 0;
         for (int64_t a = 0; a < v->n; a += bvghost::kMaxBatchNodes) {
@@ -342,8 +334,8 @@ template <typename T> int next_level(bvg_bfs* v, uint64_t at, uint64_t added, in
             rocprim::counting_iterator<int64_t> in(a);
             size_t tb = 0;
             if (rocprim::select(nullptr, tb, in, out + done, d_sel, (size_t)c, pred, g->stream) != hipSuccess) return BVG_E_HIP;
-            const int rc = v->prim.ensure(tb ? tb : 1); if (rc) return rc;
-            if (rocprim::select(v->prim.b.p, tb, in, out + done, d_sel, (size_t)c, pred, g->stream) != hipSuccess) return BVG_E_HIP;
+            const int rc = grow(v->prim, tb ? tb : 1); if (rc) return rc;
+            if (rocprim::select(v->prim.get(), tb, in, out + done, d_sel, (size_t)c, pred, g->stream) != hipSuccess) return BVG_E_HIP;
             if (ranges) {
                 unsigned long long sel = 0;
                 HIPCHK(hipMemcpyAsync(&sel, d_sel, 8, hipMemcpyDeviceToHost, g->stream));
@@ -353,7 +345,7 @@ template <typename T> int next_level(bvg_bfs* v, uint64_t at, uint64_t added, in
         }
         v->counters[kCompactedLevels]++;
     }
-    if (v->parent) hipLaunchKernelGGL((bfs_adopt_kernel<T>), dim3(grid((int64_t)added, 256)), dim3(256), 0, g->stream, (const int64_t*)out, added, (T*)v->marker.p, (T*)v->cand.p);
+    if (v->parent) hipLaunchKernelGGL((bfs_adopt_kernel<T>), dim3(grid((int64_t)added, 256)), dim3(256), 0, g->stream, (const int64_t*)out, added, (T*)v->marker.get(), (T*)v->cand.get());
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -361,9 +353,9 @@ template <typename T> int next_level(bvg_bfs* v, uint64_t at, uint64_t added, in
 // one visit from `start` (unmarked), v->round being its round already
 template <typename T> int visit_t(bvg_bfs* v, int64_t start) {
     bvg_graph* g = v->g;
-    unsigned long long* const ctl = (unsigned long long*)v->ctl.p;
-    if (v->qsize) hipLaunchKernelGGL(bfs_reset_dist_kernel, dim3(grid((int64_t)v->qsize, 256)), dim3(256), 0, g->stream, (const int64_t*)v->queue.p, v->qsize, (int32_t*)v->dist.p);
-    hipLaunchKernelGGL((bfs_seed_kernel<T>), dim3(1), dim3(64), 0, g->stream, start, v->parent ? (T)start : (T)v->round, (T*)v->marker.p, (int32_t*)v->dist.p, (int64_t*)v->queue.p);
+    unsigned long long* const ctl = v->ctl.get();
+    if (v->qsize) hipLaunchKernelGGL(bfs_reset_dist_kernel, dim3(grid((int64_t)v->qsize, 256)), dim3(256), 0, g->stream, v->queue.get(), v->qsize, v->dist.get());
+    hipLaunchKernelGGL((bfs_seed_kernel<T>), dim3(1), dim3(64), 0, g->stream, start, v->parent ? (T)start : (T)v->round, (T*)v->marker.get(), v->dist.get(), v->queue.get());
     v->cuts.assign({0, 1}); v->qsize = 1;
     int rc = budget(v); if (rc) return rc;
     if (!v->arcs_known && v->g->sh->p.arcs >= 0) { v->arcs = (uint64_t)v->g->sh->p.arcs; v->arcs_known = true; }
@@ -402,9 +394,9 @@ template <typename T> int visit_t(bvg_bfs* v, int64_t start) {
 // visit_all: need[] of the chunk [a, b)
 template <typename T> int prepare_chunk(bvg_bfs* v, int64_t a, int64_t b, size_t o_need, size_t o_deg, size_t o_ones) {
     bvg_graph* g = v->g;
-    char* const w = (char*)v->chunk_ws.b.p;
+    char* const w = v->chunk_ws.at(0);
     const int64_t cnt = b - a;
-    unsigned long long* const ctl = (unsigned long long*)v->ctl.p;
+    unsigned long long* const ctl = v->ctl.get();
     uint8_t* const need = (uint8_t*)(w + o_need); int64_t* const ones = (int64_t*)(w + o_ones);
     HIPCHK(hipMemsetAsync(ctl, 0, kCtlWords * 8, g->stream));
     outdegrees_of(g, a, b, (int32_t*)(w + o_deg));
@@ -413,13 +405,13 @@ template <typename T> int prepare_chunk(bvg_bfs* v, int64_t a, int64_t b, size_t
     HIPCHK(hipMemcpyAsync(&n_ones, ctl + kCtlCount, 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     if (n_ones) {
-        int rc = v->fr_bufs.ensure(batch_bufs_bytes((int64_t)n_ones)); if (rc) return rc;
-        const BatchBufs bb = batch_bufs_at((char*)v->fr_bufs.b.p, (int64_t)n_ones);
+        int rc = grow(v->fr_bufs, batch_bufs_bytes((int64_t)n_ones)); if (rc) return rc;
+        const BatchBufs bb = batch_bufs_at(v->fr_bufs.at(0), (int64_t)n_ones);
         uint64_t total = 0;
         rc = batch_degrees(g, bb, ones, (int64_t)n_ones, &total); if (rc) return rc;
         rc = decode_requests(v, bb, ones, (int64_t)n_ones, total); if (rc) return rc;
         hipLaunchKernelGGL(bfs_loops_kernel, dim3(grid((int64_t)n_ones, 256)), dim3(256), 0, g->stream, (const int64_t*)ones, (int64_t)n_ones, (const uint64_t*)bb.cum,
-                           (const int64_t*)v->succ.b.p, a, need);
+                           (const int64_t*)v->succ.get(), a, need);
         HIPCHK(hipGetLastError());
     }
     v->ch_a = a; v->ch_b = b;
@@ -433,10 +425,10 @@ template <typename T> int visit_all_t(bvg_bfs* v) {
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t C = (size_t)std::min(n, kChunk);
     const size_t o_need = 0, o_deg = o_need + al(C), o_ones = o_deg + al(C * 4), o_flag = o_ones + al(C * 8), o_rank = o_flag + al(C * 4), o_tmp = o_rank + al((C + 1) * 8);
-    rc = v->chunk_ws.ensure(o_tmp + al(scan_tmp_elems((int64_t)C) * 8)); if (rc) return rc;
-    char* const w = (char*)v->chunk_ws.b.p;
-    unsigned long long* const ctl = (unsigned long long*)v->ctl.p;
-    T* const marker = (T*)v->marker.p;
+    rc = grow(v->chunk_ws, o_tmp + al(scan_tmp_elems((int64_t)C) * 8)); if (rc) return rc;
+    char* const w = v->chunk_ws.at(0);
+    unsigned long long* const ctl = v->ctl.get();
+    T* const marker = (T*)v->marker.get();
     v->ch_a = v->ch_b = -1;
     for (int64_t a = 0; a < n; a += kChunk) {
         const int64_t b = std::min(n, a + kChunk);
@@ -479,15 +471,15 @@ int get_impl(bvg_bfs* v, int64_t* marker, int64_t* queue, uint64_t queue_cap, ui
     const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (marker && v->n) {
         int64_t* d_out = marker;
-        if (!dev) { int rc = v->wide_out.ensure((size_t)v->n * 8); if (rc) return rc; d_out = (int64_t*)v->wide_out.b.p; }
-        if (v->wide) hipLaunchKernelGGL((bfs_widen_kernel<uint64_t>), dim3(grid(v->n, 256)), dim3(256), 0, g->stream, (const uint64_t*)v->marker.p, v->n, d_out);
-        else hipLaunchKernelGGL((bfs_widen_kernel<uint32_t>), dim3(grid(v->n, 256)), dim3(256), 0, g->stream, (const uint32_t*)v->marker.p, v->n, d_out);
+        if (!dev) { int rc = grow(v->wide_out, (size_t)v->n * 8); if (rc) return rc; d_out = (int64_t*)v->wide_out.get(); }
+        if (v->wide) hipLaunchKernelGGL((bfs_widen_kernel<uint64_t>), dim3(grid(v->n, 256)), dim3(256), 0, g->stream, (const uint64_t*)v->marker.get(), v->n, d_out);
+        else hipLaunchKernelGGL((bfs_widen_kernel<uint32_t>), dim3(grid(v->n, 256)), dim3(256), 0, g->stream, (const uint32_t*)v->marker.get(), v->n, d_out);
         HIPCHK(hipGetLastError());
         if (!dev) HIPCHK(hipMemcpyAsync(marker, d_out, (size_t)v->n * 8, hipMemcpyDeviceToHost, g->stream));
     }
-    if (queue && v->qsize) HIPCHK(hipMemcpyAsync(queue, v->queue.p, (size_t)v->qsize * 8, kind, g->stream));
+    if (queue && v->qsize) HIPCHK(hipMemcpyAsync(queue, v->queue.get(), (size_t)v->qsize * 8, kind, g->stream));
     if (cutpoints && !v->cuts.empty()) HIPCHK(hipMemcpyAsync(cutpoints, v->cuts.data(), v->cuts.size() * 8, dev ? hipMemcpyHostToDevice : hipMemcpyHostToHost, g->stream));
-    if (dist && v->n) HIPCHK(hipMemcpyAsync(dist, v->dist.p, (size_t)v->n * 4, kind, g->stream));
+    if (dist && v->n) HIPCHK(hipMemcpyAsync(dist, v->dist.get(), (size_t)v->n * 4, kind, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     return 0;
 }
@@ -513,7 +505,7 @@ int bvg_bfs_create(bvg_graph* g, uint32_t flags, bvg_bfs** out) {
         v->per = knob_u64("BVG_BFS_BATCH_ARCS", 0);
         v->switch_den = std::max<uint64_t>(1, knob_u64("BVG_BFS_SWITCH", kSwitchDen));
         if (const char* k = knob("BVG_BFS_ROUTE")) v->force_route = !strcmp(k, "frontier") ? 1 : !strcmp(k, "sweep") ? 2 : 0;
-        if (v->marker.alloc(nn * tb) || v->dist.alloc(nn * 4) || v->queue.alloc(nn * 8) || v->ctl.alloc(256) || v->small.alloc((size_t)std::max<uint64_t>(v->small_cap, 1) * 8)) return BVG_E_NOMEM;
+        if (v->marker.alloc(nn * tb) || v->dist.alloc(nn) || v->queue.alloc(nn) || v->ctl.alloc(32) || v->small.alloc((size_t)std::max<uint64_t>(v->small_cap, 1))) return BVG_E_NOMEM;
         if (v->parent && v->cand.alloc(nn * tb)) return BVG_E_NOMEM;
         rc = clear_any(v.get()); if (rc) return rc;
         *out = v.release();
@@ -530,7 +522,7 @@ int bvg_bfs_visit(bvg_bfs* v, int64_t start, uint64_t* visited) {
     return on_device(v, [&]() -> int {
         if (start < 0 || start >= v->n) return BVG_E_ARG;
         uint64_t m = 0;                                                      // the start's marker: one element back to the host
-        HIPCHK(hipMemcpyAsync(&m, (char*)v->marker.p + (size_t)start * (v->wide ? 8 : 4), v->wide ? 8 : 4, hipMemcpyDeviceToHost, v->g->stream));
+        HIPCHK(hipMemcpyAsync(&m, (char*)v->marker.get() + (size_t)start * (v->wide ? 8 : 4), v->wide ? 8 : 4, hipMemcpyDeviceToHost, v->g->stream));
         HIPCHK(hipStreamSynchronize(v->g->stream));
         if (m != (v->wide ? ~0ull : 0xFFFFFFFFull)) return 0;                 // visited already: nothing changes (ParallelBreadthFirstVisit.java:223)
         v->round++;

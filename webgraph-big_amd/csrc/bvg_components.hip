@@ -161,30 +161,29 @@ __global__ void cc_remap_kernel(int64_t* comp, int64_t n, const uint64_t* newidx
 
 namespace {
 
-using bvghost::DevBuf;
 
 // compress + number + sizes + sort over a parent array whose trees are complete (the batch buffer is gone by now): what bvg_components
 // and bvg_scc (there parent[x] is the smallest node of x's component already) share through number_components (bvg_host.h).
 // 0 or BVG_E_CAPACITY (sizes_cap below the count; comp and the count written all the same); *count_out: the count
 template <typename T> int number_t(bvg_graph* g, T* d_parent, uint32_t flags, int64_t* comp, int64_t* sizes, uint64_t sizes_cap, uint64_t* n_components, bool dev, uint64_t* count_out) {
     const int64_t n = g->sh->p.nodes;
-    DevBuf flag, rank, tmp, dcomp;
-    if (flag.alloc((size_t)n * 4) || rank.alloc(((size_t)n + 1) * 8) || tmp.alloc(scan_tmp_elems(n) * 8)) return BVG_E_NOMEM;
+    DevArray<int32_t> flag; DevArray<uint64_t> rank, tmp; DevArray<int64_t> dcomp;
+    if (flag.alloc((size_t)n) || rank.alloc((size_t)n + 1) || tmp.alloc(scan_tmp_elems(n))) return BVG_E_NOMEM;
     int64_t* d_comp = comp;
-    if (!dev) { if (dcomp.alloc((size_t)n * 8)) return BVG_E_NOMEM; d_comp = (int64_t*)dcomp.p; }
-    hipLaunchKernelGGL((cc_compress_kernel<T>), dim3(grid(n, 256)), dim3(256), 0, g->stream, d_parent, n, (int32_t*)flag.p);
-    launch_exclusive_scan((const int32_t*)flag.p, (uint64_t*)rank.p, n, (uint64_t*)tmp.p, g->stream);
-    hipLaunchKernelGGL((cc_label_kernel<T>), dim3(grid(n, 256)), dim3(256), 0, g->stream, (const T*)d_parent, n, (const uint64_t*)rank.p, d_comp);
+    if (!dev) { if (dcomp.alloc((size_t)n)) return BVG_E_NOMEM; d_comp = dcomp; }
+    hipLaunchKernelGGL((cc_compress_kernel<T>), dim3(grid(n, 256)), dim3(256), 0, g->stream, d_parent, n, flag.get());
+    launch_exclusive_scan(flag.get(), rank.get(), n, tmp.get(), g->stream);
+    hipLaunchKernelGGL((cc_label_kernel<T>), dim3(grid(n, 256)), dim3(256), 0, g->stream, (const T*)d_parent, n, rank.get(), d_comp);
     uint64_t count = 0;
-    HIPCHK(hipMemcpyAsync(&count, (uint64_t*)rank.p + n, 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(&count, rank.get() + n, 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     if (n_components) *n_components = count;
     const bool want_sizes = sizes != nullptr || (flags & BVG_CC_SORT_BY_SIZE);
     const bool cap_ok = sizes == nullptr || sizes_cap >= count;
     if (want_sizes && count) {
-        DevBuf dsz;
+        DevArray<unsigned long long> dsz;
         unsigned long long* d_sizes = (dev && sizes && cap_ok) ? (unsigned long long*)sizes : nullptr;
-        if (!d_sizes) { if (dsz.alloc(count * 8)) return BVG_E_NOMEM; d_sizes = (unsigned long long*)dsz.p; }
+        if (!d_sizes) { if (dsz.alloc(count)) return BVG_E_NOMEM; d_sizes = dsz; }
         HIPCHK(hipMemsetAsync(d_sizes, 0, count * 8, g->stream));
         hipLaunchKernelGGL(cc_sizes_kernel, dim3(grid(n, 256)), dim3(256), 0, g->stream, (const int64_t*)d_comp, n, d_sizes);
         if (flags & BVG_CC_SORT_BY_SIZE) {
@@ -192,15 +191,15 @@ template <typename T> int number_t(bvg_graph* g, T* d_parent, uint32_t flags, in
             size_t sort_b = 0;
             if (rocprim::radix_sort_pairs(nullptr, sort_b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)count, 0u, bits, g->stream) != hipSuccess)
                 return BVG_E_HIP;
-            DevBuf keys, keys2, idx, idx2, st;                               // (idx2 doubles as the inverse permutation)
-            if (keys.alloc(count * 8) || keys2.alloc(count * 8) || idx.alloc(count * 8) || idx2.alloc(count * 8) || st.alloc(sort_b)) return BVG_E_NOMEM;
+            DevArray<uint64_t> keys, keys2, idx, idx2; DevArray<uint8_t> st;                             // (idx2 doubles as the inverse permutation)
+            if (keys.alloc(count) || keys2.alloc(count) || idx.alloc(count) || idx2.alloc(count) || st.alloc(sort_b)) return BVG_E_NOMEM;
             hipLaunchKernelGGL(cc_sort_keys_kernel, dim3(grid((int64_t)count, 256)), dim3(256), 0, g->stream, (const unsigned long long*)d_sizes, count, (uint64_t)n,
-                               (uint64_t*)keys.p, (uint64_t*)idx.p);
-            if (rocprim::radix_sort_pairs(st.p, sort_b, (const uint64_t*)keys.p, (uint64_t*)keys2.p, (const uint64_t*)idx.p, (uint64_t*)idx2.p, (size_t)count, 0u, bits, g->stream) != hipSuccess)
+                               keys.get(), idx.get());
+            if (rocprim::radix_sort_pairs(st.get(), sort_b, (const uint64_t*)keys.get(), keys2.get(), (const uint64_t*)idx.get(), idx2.get(), (size_t)count, 0u, bits, g->stream) != hipSuccess)
                 return BVG_E_HIP;
-            hipLaunchKernelGGL(cc_invert_kernel, dim3(grid((int64_t)count, 256)), dim3(256), 0, g->stream, (const uint64_t*)keys2.p, (const uint64_t*)idx2.p, count, (uint64_t)n,
-                               (uint64_t*)idx.p, d_sizes);
-            hipLaunchKernelGGL(cc_remap_kernel, dim3(grid(n, 256)), dim3(256), 0, g->stream, d_comp, n, (const uint64_t*)idx.p);
+            hipLaunchKernelGGL(cc_invert_kernel, dim3(grid((int64_t)count, 256)), dim3(256), 0, g->stream, keys2.get(), idx2.get(), count, (uint64_t)n,
+                               idx.get(), d_sizes);
+            hipLaunchKernelGGL(cc_remap_kernel, dim3(grid(n, 256)), dim3(256), 0, g->stream, d_comp, n, idx.get());
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(g->stream));
         }
@@ -221,9 +220,9 @@ template <typename T> int components_t(bvg_graph* g, uint32_t flags, int64_t* co
     const bool dbgt = dbg_on();
     Stopwatch sw;
     index_first(g);
-    DevBuf parent;
-    if (parent.alloc((size_t)n * sizeof(T))) return BVG_E_NOMEM;
-    T* const d_parent = (T*)parent.p;
+    DevArray<T> parent;
+    if (parent.alloc((size_t)n)) return BVG_E_NOMEM;
+    T* const d_parent = parent;
     hipLaunchKernelGGL((cc_init_kernel<T>), dim3(grid(n, 256)), dim3(256), 0, g->stream, d_parent, n);
     uint64_t per = 0;                                                       // (of what is free once the parent array is there)
     int rc = arc_budget(n, kMaxBatchArcs, "BVG_CC_BATCH_ARCS", &per); if (rc) return rc;
@@ -231,26 +230,26 @@ template <typename T> int components_t(bvg_graph* g, uint32_t flags, int64_t* co
     rc = sp.build(g, per); if (rc) return rc;
     const double t_plan = sw.lap();
     double t_dec = 0, t_hook = 0;
-    DevBuf d_bad;
-    if (d_bad.alloc(256)) return BVG_E_NOMEM;
-    HIPCHK(hipMemsetAsync(d_bad.p, 0, sizeof(unsigned), g->stream));
+    DevArray<unsigned> d_bad;
+    if (d_bad.alloc(64)) return BVG_E_NOMEM;
+    HIPCHK(hipMemsetAsync(d_bad.get(), 0, sizeof(unsigned), g->stream));
     if (!sp.batches.empty()) {
-        DevBuf ws;                                                          // (this scope: gone before the numbering pass, which needs the memory)
+        DevArray<uint8_t> ws;                                                    // (this scope: gone before the numbering pass, which needs the memory)
         if (ws.alloc(sp.bytes)) return BVG_E_NOMEM;                         // parent array + the largest batch: does not fit
-        sp.bind(ws.p);
+        sp.bind(ws.get());
         for (const Batch& b : sp.batches) {
             const int64_t cnt = b.hi - b.lo;
             sw.lap();
             rc = sp.decode(g, b); if (rc) return rc;
             if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); t_dec += sw.lap(); }
             hipLaunchKernelGGL((cc_hook_kernel<T>), dim3(grid(cnt, 256)), dim3(256), 0, g->stream, (const uint64_t*)sp.cum(), b.lo, cnt, (const int64_t*)sp.succ(), n, d_parent,
-                               (unsigned*)d_bad.p);
+                               d_bad.get());
             HIPCHK(hipGetLastError());
             if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); t_hook += sw.lap(); }
         }
     }
     unsigned bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, d_bad.p, sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(&bad, d_bad.get(), sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     if (bad) return BVG_E_EOF;                                              // a successor outside [0, n): malformed stream
     sw.lap();

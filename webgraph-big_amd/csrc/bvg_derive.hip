@@ -15,7 +15,7 @@
 // single-chunk launch per chunk.  A last pass numbers the record starts (prefix sum of the per-chunk counts) and writes the
 // offsets.  Anything odd in the final, exact walk (a code other than unary longer than 64 bits, a negative count, a reference beyond
 // the window, too few records) is reported, and the caller falls back to the sequential walk, whose error bits are the documented ones.
-#include "bvg_kernels.h"
+#include "bvg_host.h"
 #include "bvg_lds_codes.h"
 
 #include <cstdio>
@@ -343,22 +343,12 @@ int derive_offsets_parallel(const uint8_t* graph, uint64_t nbytes, int64_t n, in
     if (nch64 > 0x7FFFFFF0ull) return -1;
     const uint32_t nchunks = (uint32_t)nch64, R = (uint32_t)window + 1u;
     const bool gen = !is_default_codings(cod);
-    struct Bufs {
-        std::vector<void*> p;
-        void* get(size_t bytes) { void* q = nullptr; if (hipMalloc(&q, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); return nullptr; } p.push_back(q); return q; }
-        ~Bufs() { for (void* q : p) (void)hipFree(q); }
-    } B;
-    WalkState* entry = (WalkState*)B.get((size_t)nchunks * sizeof(WalkState));
-    WalkState* exitst = (WalkState*)B.get((size_t)nchunks * sizeof(WalkState));
-    uint32_t* entry_ring = (uint32_t*)B.get((size_t)nchunks * R * 4);
-    uint32_t* exit_ring = (uint32_t*)B.get((size_t)nchunks * R * 4);
-    uint32_t* counts = (uint32_t*)B.get((size_t)nchunks * 4);
-    uint32_t* lists = (uint32_t*)B.get((size_t)nchunks * 2 * 4);
-    uint32_t* d_n = (uint32_t*)B.get(16);                               // [0] mismatching chunks, [1] the first of them, [2] chunks to walk
-    int32_t* counts_i = (int32_t*)B.get((size_t)nchunks * 4);
-    uint64_t* base = (uint64_t*)B.get(((size_t)nchunks + 1) * 8);
-    uint64_t* tmp = (uint64_t*)B.get(scan_tmp_elems(nchunks) * 8);
-    if (!entry || !exitst || !entry_ring || !exit_ring || !counts || !lists || !d_n || !counts_i || !base || !tmp) return -2;
+    DevArray<WalkState> entry_o, exitst_o; DevArray<uint32_t> entry_ring_o, exit_ring_o, counts_o, lists_o, d_n_o; DevArray<int32_t> counts_i_o; DevArray<uint64_t> base_o, tmp_o;
+    if (entry_o.alloc(nchunks) || exitst_o.alloc(nchunks) || entry_ring_o.alloc((size_t)nchunks * R) || exit_ring_o.alloc((size_t)nchunks * R) || counts_o.alloc(nchunks) ||
+        lists_o.alloc((size_t)nchunks * 2) || d_n_o.alloc(4) || counts_i_o.alloc(nchunks) || base_o.alloc((size_t)nchunks + 1) || tmp_o.alloc(scan_tmp_elems(nchunks))) return -2;
+    WalkState* const entry = entry_o; WalkState* const exitst = exitst_o; uint32_t* const entry_ring = entry_ring_o; uint32_t* const exit_ring = exit_ring_o;
+    uint32_t* const counts = counts_o; uint32_t* const lists = lists_o; int32_t* const counts_i = counts_i_o; uint64_t* const base = base_o; uint64_t* const tmp = tmp_o;
+    uint32_t* const d_n = d_n_o;                                         // [0] mismatching chunks, [1] the first of them, [2] chunks to walk
     hipLaunchKernelGGL(derive_init_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, s, nchunks, entry, entry_ring, R);
     uint32_t Rp = 1; while (Rp < R) Rp <<= 1;
     const size_t lds = (size_t)Rp * 64 * 4;

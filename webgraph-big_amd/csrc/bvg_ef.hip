@@ -38,10 +38,11 @@ struct EfView {
 struct EfShared {
     int device = 0;
     bvg_ef_params p{};
-    uint64_t* d_words = nullptr; uint64_t nwords = 0; bool own_words = false;
-    uint64_t* d_offsets = nullptr;
+    const uint64_t* d_words = nullptr; uint64_t nwords = 0; DevArray<uint64_t> own_words;   // d_words: what the kernels read; own_words holds it unless it is the caller's
+    DevArray<uint64_t> d_offsets;
     uint64_t total_bits = 0;
     std::atomic<int> refs{1};
+    ~EfShared() { (void)hipSetDevice(device); }
 };
 
 }  // namespace
@@ -50,8 +51,14 @@ struct bvg_efgraph {
     EfShared* sh = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    void* ws = nullptr; size_t ws_bytes = 0;      // per-call arrays (below), grown on demand
-    void* out_ws = nullptr; size_t out_bytes = 0; // successors of a host-buffer call
+    DevWorkspace ws;                              // per-call arrays (below), grown on demand
+    DevWorkspace out_ws;                          // successors of a host-buffer call
+    ~bvg_efgraph() {
+        if (sh) (void)hipSetDevice(sh->device);
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
 };
 
 namespace {
@@ -311,21 +318,16 @@ void ef_host_words(const uint8_t* bytes, uint64_t nbytes, bool big_endian, std::
 }
 
 int ef_make_handle(EfShared* sh, bvg_efgraph** out) {
-    bvg_efgraph* g = new bvg_efgraph();
+    std::unique_ptr<bvg_efgraph> g(new bvg_efgraph());
     g->sh = sh;
-    auto fail = [&](int code) { if (g->stream) (void)hipStreamDestroy(g->stream); if (g->ev0) (void)hipEventDestroy(g->ev0); if (g->ev1) (void)hipEventDestroy(g->ev1); delete g; return code; };
     if (hipSetDevice(sh->device) != hipSuccess || hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&g->ev0) != hipSuccess || hipEventCreate(&g->ev1) != hipSuccess) { (void)hipGetLastError(); return fail(BVG_E_HIP); }
-    *out = g;
+        hipEventCreate(&g->ev0) != hipSuccess || hipEventCreate(&g->ev1) != hipSuccess) { (void)hipGetLastError(); return BVG_E_HIP; }
+    *out = g.release();
     return 0;
 }
 
 void ef_release(EfShared* sh) {
-    if (sh->refs.fetch_sub(1) != 1) return;
-    (void)hipSetDevice(sh->device);
-    if (sh->own_words && sh->d_words) (void)hipFree(sh->d_words);
-    if (sh->d_offsets) (void)hipFree(sh->d_offsets);
-    delete sh;
+    if (sh->refs.fetch_sub(1) == 1) delete sh;
 }
 
 // words: host (copied) or device (adopted); offsets: host or device (copied), one of them non-null
@@ -333,28 +335,22 @@ int ef_open_common(const bvg_ef_params& p, const uint64_t* h_words, const void* 
                    const void* d_offsets_in, int device, bvg_efgraph** out) {
     int r = ef_check_params(p); if (r) return r;
     r = ensure_device(device); if (r) return r;
-    EfShared* sh = new EfShared();
+    struct Release { void operator()(EfShared* s) const { ef_release(s); } };
+    std::unique_ptr<EfShared, Release> owner(new EfShared());   // released on every return but the last
+    EfShared* sh = owner.get();
     sh->device = device; sh->p = p; sh->nwords = nwords;
-    auto fail = [&](int code) { ef_release(sh); return code; };
     const size_t n1 = (size_t)p.nodes + 1;
-    if (d_words_in) sh->d_words = (uint64_t*)d_words_in;
+    if (d_words_in) sh->d_words = (const uint64_t*)d_words_in;
     else {
-        if (hipMalloc(&sh->d_words, (size_t)(nwords ? nwords : 1) * 8) != hipSuccess) { (void)hipGetLastError(); sh->d_words = nullptr; return fail(BVG_E_NOMEM); }
-        sh->own_words = true;
-        if (nwords && hipMemcpy(sh->d_words, h_words, (size_t)nwords * 8, hipMemcpyHostToDevice) != hipSuccess) return fail(BVG_E_HIP);
+        if (sh->own_words.alloc((size_t)nwords)) return BVG_E_NOMEM;
+        sh->d_words = sh->own_words;
+        if (nwords && hipMemcpy(sh->own_words, h_words, (size_t)nwords * 8, hipMemcpyHostToDevice) != hipSuccess) return BVG_E_HIP;
     }
-    if (hipMalloc(&sh->d_offsets, n1 * 8) != hipSuccess) { (void)hipGetLastError(); sh->d_offsets = nullptr; return fail(BVG_E_NOMEM); }
-    if (hipMemcpy(sh->d_offsets, h_offsets ? (const void*)h_offsets : d_offsets_in, n1 * 8, h_offsets ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice) != hipSuccess) return fail(BVG_E_HIP);
-    if (hipMemcpy(&sh->total_bits, sh->d_offsets + p.nodes, 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(BVG_E_HIP);
-    r = ef_make_handle(sh, out);
-    return r ? fail(r) : 0;
-}
-
-int ef_ensure(void** p, size_t* have, size_t bytes) {
-    if (*have >= bytes) return 0;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
-    if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return BVG_E_NOMEM; }
-    *have = bytes;
+    if (sh->d_offsets.alloc(n1)) return BVG_E_NOMEM;
+    if (hipMemcpy(sh->d_offsets, h_offsets ? (const void*)h_offsets : d_offsets_in, n1 * 8, h_offsets ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice) != hipSuccess) return BVG_E_HIP;
+    if (hipMemcpy(&sh->total_bits, sh->d_offsets + p.nodes, 8, hipMemcpyDeviceToHost) != hipSuccess) return BVG_E_HIP;
+    r = ef_make_handle(sh, out); if (r) return r;
+    (void)owner.release();
     return 0;
 }
 
@@ -371,8 +367,8 @@ int ef_bufs(bvg_efgraph* g, int64_t count, bool with_nodes, EfBufs& b) {
     const size_t s_deg = ef_align((c + 1) * 4), s_cum = ef_align((c + 1) * 8), s_tmp = ef_align(scan_tmp_elems(count) * 8 + 8), s_long = ef_align(c * 4 + 4),
                  s_flags = 256, s_acc = ef_align(kEfStripes * 8), s_nodes = with_nodes ? ef_align(c * 8 + 8) : 0;
     const size_t total = 2 * s_deg + 2 * s_cum + s_tmp + s_long + s_flags + s_acc + s_nodes;
-    const int r = ef_ensure(&g->ws, &g->ws_bytes, total); if (r) return r;
-    char* p = (char*)g->ws;
+    const int r = g->ws.reserve(total); if (r) return r;
+    char* p = g->ws.at(0);
     b.deg = (int32_t*)p; p += s_deg; b.pw = (int32_t*)p; p += s_deg; b.acum = (uint64_t*)p; p += s_cum; b.wcum = (uint64_t*)p; p += s_cum;
     b.tmp = (uint64_t*)p; p += s_tmp; b.longlist = (uint32_t*)p; p += s_long; b.flags = (unsigned*)p; p += s_flags; b.acc = (unsigned long long*)p; p += s_acc;
     b.nodes = with_nodes ? (int64_t*)p : nullptr;
@@ -448,7 +444,7 @@ int ef_decode_impl(bvg_efgraph* g, const int64_t* h_nodes, int64_t from, int64_t
     *n_succ = total;
     if (total > cap || (!succ && total)) return BVG_E_CAPACITY;
     int64_t* d_out = succ;
-    if (!dev) { r = ef_ensure(&g->out_ws, &g->out_bytes, (size_t)(total ? total : 1) * 8); if (r) return r; d_out = (int64_t*)g->out_ws; }
+    if (!dev) { r = g->out_ws.reserve((size_t)(total ? total : 1) * 8); if (r) return r; d_out = (int64_t*)g->out_ws.get(); }
     int status = 0; uint64_t at = 0;
     for (int64_t c = 0; c < nchunks; c++) {
         const int64_t lo = c * chunk, cnt = std::min(chunk, count - lo);
@@ -606,14 +602,9 @@ int bvg_ef_copy(const bvg_efgraph* g, bvg_efgraph** out) {
 
 void bvg_ef_close(bvg_efgraph* g) {
     if (!g) return;
-    (void)hipSetDevice(g->sh->device);
-    if (g->stream) { (void)hipStreamSynchronize(g->stream); (void)hipStreamDestroy(g->stream); }
-    if (g->ev0) (void)hipEventDestroy(g->ev0);
-    if (g->ev1) (void)hipEventDestroy(g->ev1);
-    if (g->ws) (void)hipFree(g->ws);
-    if (g->out_ws) (void)hipFree(g->out_ws);
-    ef_release(g->sh);
+    EfShared* const sh = g->sh;
     delete g;
+    ef_release(sh);
 }
 
 int bvg_ef_info(const bvg_efgraph* g, bvg_ef_params* out) { if (!g || !out) return BVG_E_ARG; *out = g->sh->p; return 0; }
@@ -669,9 +660,9 @@ int bvg_ef_skip_to_batch(bvg_efgraph* g, const int64_t* nodes, const int64_t* bo
         HIPCHK(hipSetDevice(g->sh->device));
         hipStream_t s = g->stream;
         const size_t c8 = ef_align((size_t)count * 8);
-        int r = ef_ensure(&g->out_ws, &g->out_bytes, 3 * c8 + 256); if (r) return r;
-        int64_t* dn = (int64_t*)g->out_ws; int64_t* db = (int64_t*)((char*)g->out_ws + c8); int64_t* dout = (int64_t*)((char*)g->out_ws + 2 * c8);
-        unsigned* flags = (unsigned*)((char*)g->out_ws + 3 * c8);
+        int r = g->out_ws.reserve(3 * c8 + 256); if (r) return r;
+        int64_t* dn = (int64_t*)g->out_ws.at(0); int64_t* db = (int64_t*)g->out_ws.at(c8); int64_t* dout = (int64_t*)g->out_ws.at(2 * c8);
+        unsigned* flags = (unsigned*)g->out_ws.at(3 * c8);
         HIPCHK(hipMemsetAsync(flags, 0, 256, s));
         HIPCHK(hipMemcpyAsync(dn, nodes, (size_t)count * 8, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(db, bounds, (size_t)count * 8, hipMemcpyHostToDevice, s));
@@ -710,30 +701,28 @@ int bvg_ef_store(int64_t nodes, int64_t upper_bound, int log2_quantum, int big_e
         int r = ensure_device(device); if (r) return r;
         // sizes from outdegrees -> prefix sum: record lengths exceed 32 bits long before outdegrees do, and the CSR offsets are host memory
         // already, so this serial sum (a few operations per node, as the derivation at load) runs on the host
-        uint64_t* ho = (uint64_t*)malloc(((size_t)nodes + 1) * 8);
-        uint8_t* hg = nullptr;
+        HostArray<uint64_t> ho((uint64_t*)malloc(((size_t)nodes + 1) * 8));
         if (!ho) return BVG_E_NOMEM;
         ho[0] = 0;
         for (int64_t x = 0; x < nodes; x++) ho[x + 1] = ef_geom(ho[x], adj_off[x + 1] - adj_off[x], (uint64_t)upper_bound, (uint32_t)log2_quantum).end;
         const uint64_t nwords = ho[nodes] / 64 + 1;                                   // close() always writes the current word (EF:408-413)
-        DevBuf d_off, d_adj, d_offsets, d_words, d_bad;
-        auto fail = [&](int code) { free(ho); free(hg); return code; };
-        if (d_off.alloc(((size_t)nodes + 1) * 8) || d_adj.alloc((size_t)(m ? m : 1) * 8) || d_offsets.alloc(((size_t)nodes + 1) * 8) || d_words.alloc((size_t)nwords * 8) || d_bad.alloc(4)) return fail(BVG_E_NOMEM);
-        if (hipMemcpy(d_off.p, adj_off, ((size_t)nodes + 1) * 8, hipMemcpyHostToDevice) != hipSuccess || (m && hipMemcpy(d_adj.p, adj, (size_t)m * 8, hipMemcpyHostToDevice) != hipSuccess) ||
-            hipMemcpy(d_offsets.p, ho, ((size_t)nodes + 1) * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d_bad.p, 0, 4) != hipSuccess || hipMemset(d_words.p, 0, (size_t)nwords * 8) != hipSuccess) return fail(BVG_E_HIP);
-        const uint64_t* p_off = (const uint64_t*)d_off.p; const int64_t* p_adj = (const int64_t*)d_adj.p; const uint64_t* p_offsets = (const uint64_t*)d_offsets.p;
-        unsigned long long* p_words = (unsigned long long*)d_words.p; unsigned* p_bad = (unsigned*)d_bad.p;
+        DevArray<uint64_t> d_off, d_offsets; DevArray<int64_t> d_adj; DevArray<unsigned long long> d_words; DevArray<unsigned> d_bad;
+        if (d_off.alloc((size_t)nodes + 1) || d_adj.alloc((size_t)m) || d_offsets.alloc((size_t)nodes + 1) || d_words.alloc((size_t)nwords) || d_bad.alloc(1)) return BVG_E_NOMEM;
+        if (hipMemcpy(d_off, adj_off, ((size_t)nodes + 1) * 8, hipMemcpyHostToDevice) != hipSuccess || (m && hipMemcpy(d_adj, adj, (size_t)m * 8, hipMemcpyHostToDevice) != hipSuccess) ||
+            hipMemcpy(d_offsets, ho.get(), ((size_t)nodes + 1) * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d_bad, 0, 4) != hipSuccess || hipMemset(d_words, 0, (size_t)nwords * 8) != hipSuccess) return BVG_E_HIP;
+        const uint64_t* p_off = d_off; const int64_t* p_adj = d_adj; const uint64_t* p_offsets = d_offsets;
+        unsigned long long* p_words = d_words; unsigned* p_bad = d_bad;
         const uint64_t ub = (uint64_t)upper_bound; const uint32_t q = (uint32_t)log2_quantum;
         unsigned hb = 0;
         if (nodes) hipLaunchKernelGGL(ef_store_check_kernel, dim3(grid(nodes, 256)), dim3(256), 0, 0, p_off, p_adj, nodes, p_bad);
-        if (hipMemcpy(&hb, p_bad, 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(BVG_E_HIP);
-        if (hb) return fail(BVG_E_ARG);
+        if (hipMemcpy(&hb, p_bad, 4, hipMemcpyDeviceToHost) != hipSuccess) return BVG_E_HIP;
+        if (hb) return BVG_E_ARG;
         if (nodes) hipLaunchKernelGGL(ef_store_write_kernel, dim3(grid((int64_t)(m + (uint64_t)nodes), 256)), dim3(256), 0, 0, ub, q, p_off, p_adj, nodes, p_offsets, p_words);
         if (big_endian) hipLaunchKernelGGL(ef_bswap_kernel, dim3(grid((int64_t)nwords, 256)), dim3(256), 0, 0, p_words, nwords);
-        hg = (uint8_t*)malloc((size_t)nwords * 8);
-        if (!hg) return fail(BVG_E_NOMEM);
-        if (hipMemcpy(hg, d_words.p, (size_t)nwords * 8, hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess) return fail(BVG_E_HIP);
-        *graph = hg; *graph_bytes = nwords * 8; *offsets = ho;
+        HostArray<uint8_t> hg((uint8_t*)malloc((size_t)nwords * 8));
+        if (!hg) return BVG_E_NOMEM;
+        if (hipMemcpy(hg.get(), p_words, (size_t)nwords * 8, hipMemcpyDeviceToHost) != hipSuccess || hipGetLastError() != hipSuccess) return BVG_E_HIP;
+        *graph = hg.release(); *graph_bytes = nwords * 8; *offsets = ho.release();
         return 0;
     });
 }

@@ -21,7 +21,7 @@
 #include <cstring>
 #include <vector>
 
-#include "bvg_kernels.h"
+#include "bvg_host.h"
 
 namespace bvg {
 
@@ -274,7 +274,7 @@ __global__ void enc_check_kernel(const uint64_t* adj_off, const int64_t* adj, in
 
 }  // namespace
 
-// Device-side store: adjacency already in HBM.  d_graph_out / d_offsets_out are hipMalloc'ed here (caller frees with hipFree);
+// Device-side store: adjacency already in HBM.  d_graph_out / d_offsets_out are allocated here and released to the caller (who adopt()s them);
 // *graph_bytes = ceil(offsets[n] / 8).  Returns a bvg status.
 int encode_store_dev(const bvg_params& bp, const uint64_t* d_adj_off, const int64_t* d_adj, int64_t n, int64_t chunk_nodes, hipStream_t s,
                      uint8_t** d_graph_out, uint64_t* graph_bytes, uint64_t** d_offsets_out) {
@@ -282,48 +282,37 @@ int encode_store_dev(const bvg_params& bp, const uint64_t* d_adj_off, const int6
     EncParams p{bp.window_size, bp.max_ref_count, bp.min_interval_length, bp.zeta_k, bp.outdegree_coding, bp.block_coding, bp.residual_coding,
                 bp.reference_coding, bp.block_count_coding, n, chunk_nodes > 0 ? chunk_nodes : 0};
     const int cyc = p.W + 1;
-    uint32_t* sizes = nullptr; uint8_t* best = nullptr; int32_t* recbits = nullptr; uint64_t* offsets = nullptr; uint64_t* tmp = nullptr; unsigned* bad = nullptr;
-    uint8_t* graph = nullptr;
-    auto done = [&](int code) {
-        for (void* q : {(void*)sizes, (void*)best, (void*)recbits, (void*)tmp, (void*)bad}) if (q) (void)hipFree(q);
-        if (code) { if (offsets) (void)hipFree(offsets); if (graph) (void)hipFree(graph); }
-        return code;
-    };
+    DevArray<uint32_t> sizes_o; DevArray<uint8_t> best_o, graph_o; DevArray<int32_t> recbits_o; DevArray<uint64_t> offsets_o, tmp_o; DevArray<unsigned> bad_o;
     const size_t nn = (size_t)(n > 0 ? n : 1);
-#define ENC_CHK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { (void)hipGetLastError(); return done(_e == hipErrorOutOfMemory ? BVG_E_NOMEM : BVG_E_HIP); } } while (0)
-    ENC_CHK(hipMalloc(&sizes, nn * (size_t)cyc * sizeof(uint32_t)));
-    ENC_CHK(hipMalloc(&best, nn));
-    ENC_CHK(hipMalloc(&recbits, nn * sizeof(int32_t)));
-    ENC_CHK(hipMalloc(&offsets, (nn + 1) * sizeof(uint64_t)));
-    ENC_CHK(hipMalloc(&tmp, scan_tmp_elems((int64_t)nn) * sizeof(uint64_t)));
-    ENC_CHK(hipMalloc(&bad, sizeof(unsigned)));
-    ENC_CHK(hipMemsetAsync(bad, 0, sizeof(unsigned), s));
-    ENC_CHK(hipMemsetAsync(offsets, 0, (nn + 1) * sizeof(uint64_t), s));
+    if (sizes_o.alloc(nn * (size_t)cyc) || best_o.alloc(nn) || recbits_o.alloc(nn) || offsets_o.alloc(nn + 1) || tmp_o.alloc(scan_tmp_elems((int64_t)nn)) || bad_o.alloc(1)) return BVG_E_NOMEM;
+    uint32_t* const sizes = sizes_o; uint8_t* const best = best_o; int32_t* const recbits = recbits_o; uint64_t* const offsets = offsets_o; uint64_t* const tmp = tmp_o; unsigned* const bad = bad_o;
+    HIPCHK(hipMemsetAsync(bad, 0, sizeof(unsigned), s));
+    HIPCHK(hipMemsetAsync(offsets, 0, (nn + 1) * sizeof(uint64_t), s));
     uint64_t total_bits = 0;
     if (n > 0) {
         hipLaunchKernelGGL(enc_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_adj_off, d_adj, n, bad);
         unsigned hb = 0;
-        ENC_CHK(hipMemcpyAsync(&hb, bad, sizeof hb, hipMemcpyDeviceToHost, s));
-        ENC_CHK(hipStreamSynchronize(s));
-        if (hb) return done(BVG_E_ARG);
+        HIPCHK(hipMemcpyAsync(&hb, bad, sizeof hb, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (hb) return BVG_E_ARG;
         const int64_t pairs = n * cyc;
         hipLaunchKernelGGL(enc_sizes_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, p, d_adj_off, d_adj, sizes);
         const int64_t cn = p.chunk_nodes > 0 ? p.chunk_nodes : n;
         const int64_t nchunks = (n + cn - 1) / cn;
         hipLaunchKernelGGL(enc_choose_kernel, dim3((unsigned)nchunks), dim3(64), (size_t)(64 * cyc + cyc + 3 * 64) * sizeof(uint32_t), s, p, d_adj_off, sizes, best, recbits);
         launch_exclusive_scan(recbits, offsets, n, tmp, s);
-        ENC_CHK(hipMemcpyAsync(&total_bits, offsets + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        ENC_CHK(hipStreamSynchronize(s));
+        HIPCHK(hipMemcpyAsync(&total_bits, offsets + n, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
     }
     const uint64_t nbytes = (total_bits + 7) / 8;
     const size_t alloc = (size_t)((nbytes + 15) & ~15ull) + 64;           // zero padded: the decoder's loads may run past the end
-    ENC_CHK(hipMalloc(&graph, alloc));
-    ENC_CHK(hipMemsetAsync(graph, 0, alloc, s));
+    if (graph_o.alloc(alloc)) return BVG_E_NOMEM;
+    uint8_t* const graph = graph_o;
+    HIPCHK(hipMemsetAsync(graph, 0, alloc, s));
     if (n > 0) hipLaunchKernelGGL(enc_write_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, d_adj_off, d_adj, best, offsets, reinterpret_cast<uint32_t*>(graph));
-    ENC_CHK(hipStreamSynchronize(s));
-#undef ENC_CHK
-    *d_graph_out = graph; *graph_bytes = nbytes; *d_offsets_out = offsets;
-    return done(0);
+    HIPCHK(hipStreamSynchronize(s));
+    *d_graph_out = graph_o.release(); *graph_bytes = nbytes; *d_offsets_out = offsets_o.release();
+    return 0;
 }
 
 }  // namespace bvg

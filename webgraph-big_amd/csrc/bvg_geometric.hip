@@ -179,7 +179,6 @@ __global__ void geo_finish_kernel(int count, double coeff0, const double* acc, c
 namespace {
 
 using bvghost::Batch;
-using bvghost::DevBuf;
 
 enum : int { kPasses, kSweeps, kDecodes, kWordsUsed, kDeepest, kSkippedLevels, kResident, kReserved };   // bvg_geometric's counters
 
@@ -205,21 +204,21 @@ template <int W> int geometric_t(bvg_graph* g, const Coefficients& coeff, int64_
     uint64_t counters[BVG_GEO_COUNTERS] = {};
     // seen | frontier | next in one allocation (zeroed together at the start of a pass), then the accumulators
     const size_t words = (size_t)n * W;
-    DevBuf bits, accb, ws, oc, orr;
-    if (bits.alloc(words * 3 * 8) || accb.alloc((size_t)S * 24 + kCtlWords * 8)) return BVG_E_NOMEM;
-    uint64_t* const seen = (uint64_t*)bits.p; uint64_t* const frontier = seen + words; uint64_t* const next = frontier + words;
-    double* const acc = (double*)accb.p;
-    unsigned long long* const reach = (unsigned long long*)accb.p + S; unsigned long long* const cnt = reach + S; unsigned long long* const ctl = cnt + S;
+    DevArray<uint64_t> bits; DevArray<unsigned long long> accb; DevArray<uint8_t> ws; DevArray<float> oc; DevArray<int64_t> orr;
+    if (bits.alloc(words * 3) || accb.alloc((size_t)S * 3 + kCtlWords)) return BVG_E_NOMEM;
+    uint64_t* const seen = bits; uint64_t* const frontier = seen + words; uint64_t* const next = frontier + words;
+    double* const acc = (double*)accb.get();
+    unsigned long long* const reach = accb + S; unsigned long long* const cnt = reach + S; unsigned long long* const ctl = cnt + S;
     float* d_c = out.centrality; int64_t* d_r = out.reachable;
     if (!dev) {
-        if (out.centrality) { if (oc.alloc((size_t)count * 4)) return BVG_E_NOMEM; d_c = (float*)oc.p; }
-        if (out.reachable) { if (orr.alloc((size_t)count * 8)) return BVG_E_NOMEM; d_r = (int64_t*)orr.p; }
+        if (out.centrality) { if (oc.alloc((size_t)count)) return BVG_E_NOMEM; d_c = oc; }
+        if (out.reachable) { if (orr.alloc((size_t)count)) return BVG_E_NOMEM; d_r = orr; }
     }
     uint64_t per = 0;                                                       // (of what is free once the per-node arrays are there)
     int rc = arc_budget(n, kMaxBatchArcs, "BVG_GEO_BATCH_ARCS", &per); if (rc) return rc;
     bvghost::SweepPlan sp;
     rc = sp.build(g, per); if (rc) return rc;
-    if (!sp.batches.empty()) { if (ws.alloc(sp.bytes)) return BVG_E_NOMEM; sp.bind(ws.p); }
+    if (!sp.batches.empty()) { if (ws.alloc(sp.bytes)) return BVG_E_NOMEM; sp.bind(ws.get()); }
     counters[kWordsUsed] = W; counters[kResident] = sp.single() ? 1 : 0;
     HIPCHK(hipMemsetAsync(ctl, 0, kCtlWords * 8, g->stream));
     std::vector<uint64_t> hist(1, 0);
@@ -228,7 +227,7 @@ template <int W> int geometric_t(bvg_graph* g, const Coefficients& coeff, int64_
         const int in_pass = (int)std::min<int64_t>(S, to - s0);
         counters[kPasses]++;
         hist[0] += (uint64_t)in_pass;
-        HIPCHK(hipMemsetAsync(bits.p, 0, words * 3 * 8, g->stream));
+        HIPCHK(hipMemsetAsync(bits, 0, words * 3 * 8, g->stream));
         hipLaunchKernelGGL((geo_seed_kernel<W>), dim3((S + 255) / 256), dim3(256), 0, g->stream, seen, frontier, s0, in_pass, acc, reach, cnt);
         for (uint64_t d = 1;; d++) {
             for (const Batch& b : sp.batches) {

@@ -30,11 +30,13 @@
 
 using namespace bvg;
 
+// the one check of a HIP call in host code: a bvg status out of the enclosing function (whatever it owns frees itself), HIP's last error cleared
 #define HIPCHK(expr)                                                                          \
     do {                                                                                      \
         hipError_t _e = (expr);                                                               \
         if (_e != hipSuccess) {                                                               \
             if (dbg_on()) fprintf(stderr, "[bvg] %s -> %s (%s:%d)\n", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+            (void)hipGetLastError();                                                          \
             return _e == hipErrorOutOfMemory ? BVG_E_NOMEM : BVG_E_HIP;                         \
         }                                                                                     \
     } while (0)
@@ -49,13 +51,57 @@ constexpr uint32_t kGiantResident = 512;        // giant workgroups (512 threads
 constexpr uint32_t kGiantSlots = 768;           // their work areas: half as many again (a free one always turns up)
 static uint32_t giant_slots() { if (knob("BVG_GSLOTS")) { const int v = atoi(knob("BVG_GSLOTS")); if (v >= 1 && v <= 8192) return (uint32_t)v; } return kGiantSlots; }   // (experiments)
 
-// a device allocation freed on every return path
-struct DevBuf {
-    void* p = nullptr;
-    DevBuf() = default; DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
-    int alloc(size_t bytes) { if (hipMalloc(&p, bytes ? bytes : 1) == hipSuccess) return 0; p = nullptr; (void)hipGetLastError(); return 1; }
-    void* release() { void* q = p; p = nullptr; return q; }
-    ~DevBuf() { if (p) (void)hipFree(p); }
+// ---- device memory: every block the host code allocates belongs to one of these two owners, which free it when they go out of scope or when the
+// handle that holds them is deleted.  Nothing else calls hipMalloc / hipFree.  A failed allocation leaves the owner empty and HIP's last error cleared.
+
+// a typed device array: move-only, freed on every return path
+template <typename T> class DevArray {
+    T* p_ = nullptr; size_t n_ = 0;
+public:
+    DevArray() = default; DevArray(const DevArray&) = delete; DevArray& operator=(const DevArray&) = delete;
+    DevArray(DevArray&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+    DevArray& operator=(DevArray&& o) noexcept { if (this != &o) { reset(); p_ = o.p_; n_ = o.n_; o.p_ = nullptr; o.n_ = 0; } return *this; }
+    ~DevArray() { reset(); }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; n_ = 0; }
+    // `count` elements (0: one) in place of what it held: 0 or BVG_E_NOMEM
+    int alloc(size_t count) {
+        reset();
+        if (hipMalloc((void**)&p_, (count ? count : 1) * sizeof(T)) != hipSuccess) { p_ = nullptr; (void)hipGetLastError(); return BVG_E_NOMEM; }
+        n_ = count;
+        return 0;
+    }
+    void adopt(T* p, size_t count = 0) { reset(); p_ = p; n_ = count; }   // a block another function allocated and handed over
+    T* release() { T* q = p_; p_ = nullptr; n_ = 0; return q; }            // ... and the way a block leaves: to the caller, or to another owner's adopt()
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    size_t count() const { return n_; }
+};
+
+// host memory that leaves through the C ABI is malloc'ed (the caller frees it with bvg_free): owned like this until it is released to the caller
+struct HostFree { void operator()(void* p) const { free(p); } };
+template <typename T> using HostArray = std::unique_ptr<T[], HostFree>;
+
+// a workspace kept between calls, grown on demand and never shrunk.  reserve(): the block it holds when that is large enough; otherwise that block is freed first
+// and one of `bytes` taken -- or, when that fails and the caller can do with less, one of `at_least`.  0 or BVG_E_NOMEM, and then it is empty.
+class DevWorkspace {
+    void* p_ = nullptr; size_t bytes_ = 0;
+public:
+    DevWorkspace() = default; DevWorkspace(const DevWorkspace&) = delete; DevWorkspace& operator=(const DevWorkspace&) = delete;
+    ~DevWorkspace() { reset(); }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; bytes_ = 0; }
+    int reserve(size_t bytes, size_t at_least = 0) {
+        if (bytes <= bytes_) return 0;
+        reset();
+        for (size_t want : {bytes, at_least}) {
+            if (!want) break;
+            if (hipMalloc(&p_, want) == hipSuccess) { bytes_ = want; return 0; }
+            p_ = nullptr; (void)hipGetLastError();
+        }
+        return BVG_E_NOMEM;
+    }
+    void* get() const { return p_; }
+    char* at(size_t offset) const { return (char*)p_ + offset; }
+    size_t bytes() const { return bytes_; }
 };
 
 // Residual skip index of the plan blocks [blk_lo, blk_hi) (a shard builds only its own blocks; everything outside has no entries and
@@ -64,7 +110,7 @@ struct DevBuf {
 struct SkipIndex {
     int device = 0;
     uint32_t blk_lo = 0, blk_hi = 0;
-    uint64_t total = 0; uint64_t* d_first = nullptr; uint16_t* d_bit = nullptr; void* d_val = nullptr; uint8_t* d_fmt = nullptr;
+    uint64_t total = 0; DevArray<uint64_t> d_first; DevArray<uint16_t> d_bit; DevArray<uint8_t> d_val; DevArray<uint8_t> d_fmt;   // d_val: 32- or 64-bit values (`wide`)
     bool wide = false;                        // entries hold 64-bit values (built by the 64-bit kernels); a handle running the other width ignores the index
     uint32_t skip_min = kSkipMin, skip_shift = 4;   // granularity: lists of >= skip_min residuals hold one entry per 2^skip_shift residuals (skip_granularity() when it is built)
     bool failed = false;                      // the build of [blk_lo, blk_hi) failed: no arrays; scans of those blocks run index-less.  WHY it failed decides what happens next:
@@ -87,19 +133,13 @@ struct SkipIndex {
     std::vector<uint64_t> h_first;            // nblk + 1 entry indices (host copy: index_bytes of a range)
     std::vector<uint8_t> h_fmt;               // host copy of d_fmt: 1 = validated by the row kernel (the lean scan kernel may take the block)
     SkipIndex() = default; SkipIndex(const SkipIndex&) = delete; SkipIndex& operator=(const SkipIndex&) = delete;
-    ~SkipIndex() {
-        (void)hipSetDevice(device);
-        if (d_first) (void)hipFree(d_first);
-        if (d_bit) (void)hipFree(d_bit);
-        if (d_val) (void)hipFree(d_val);
-        if (d_fmt) (void)hipFree(d_fmt);
-    }
+    ~SkipIndex() { (void)hipSetDevice(device); }
 };
 
 struct Plan {
     uint32_t block_bits = 0;
     uint32_t nblk = 0;
-    uint64_t* d_first = nullptr; uint32_t* d_halo = nullptr; uint64_t* d_mask = nullptr;
+    DevArray<uint64_t> d_first; DevArray<uint32_t> d_halo; DevArray<uint64_t> d_mask;
     std::vector<uint64_t> h_first;
     std::vector<uint32_t> h_maxd;             // largest (list + the W lists before it) a block decodes: predicts its tier
     uint64_t version = 0;
@@ -108,10 +148,7 @@ struct Plan {
     std::shared_ptr<struct SkipIndex> skip;
     void release() {
         std::atomic_store(&skip, std::shared_ptr<struct SkipIndex>());
-        if (d_first) (void)hipFree(d_first);
-        if (d_halo) (void)hipFree(d_halo);
-        if (d_mask) (void)hipFree(d_mask);
-        d_first = nullptr; d_halo = nullptr; d_mask = nullptr; nblk = 0; h_first.clear(); h_maxd.clear();
+        d_first.reset(); d_halo.reset(); d_mask.reset(); nblk = 0; h_first.clear(); h_maxd.clear();
     }
     int device = 0;
     Plan() = default;
@@ -123,10 +160,10 @@ struct Plan {
 struct Shared {
     int device = 0;
     bvg_params p{};
-    uint8_t* d_graph = nullptr; uint64_t nbytes = 0; uint64_t padded = 0; bool own_graph = false;
+    uint8_t* d_graph = nullptr; uint64_t nbytes = 0; uint64_t padded = 0; DevArray<uint8_t> own_graph;   // d_graph: what the kernels read; own_graph holds it unless it is the caller's (bvg_open_dev)
     // the offsets index: packed (owned: 4 bytes per node + 8 per 2^kOffShift nodes) or, as a fallback, the plain 64-bit array
     Offsets offs{nullptr, nullptr, nullptr};
-    uint32_t* d_off_lo = nullptr; uint64_t* d_off_hi = nullptr; uint64_t* d_off_wide = nullptr; bool own_wide = false;
+    DevArray<uint32_t> d_off_lo; DevArray<uint64_t> d_off_hi; DevArray<uint64_t> own_wide;   // what offs points into (a caller's plain array is not held)
     uint64_t offsets_bytes() const { return offs.lo ? ((uint64_t)p.nodes + 1) * 4 + ((((uint64_t)p.nodes + 1) >> kOffShift) + 1) * 8 : ((uint64_t)p.nodes + 1) * 8; }
     uint64_t total_bits = 0;
     bool wide = false;
@@ -139,6 +176,7 @@ struct Shared {
     // cached shard bounds (bvg_shard_bounds): key = (k << 2) | balance
     std::map<uint64_t, std::vector<int64_t>> shard_bounds; std::mutex shard_mu;
     std::atomic<int> refs{1};
+    ~Shared() { (void)hipSetDevice(device); }
 };
 
 
@@ -149,29 +187,37 @@ struct bvg_graph {
     Shared* sh = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    unsigned long long* d_acc = nullptr;      // 4 result words + 8 debug counters
-    uint32_t* d_fail = nullptr;               // [0] count, [1..] list
+    DevArray<unsigned long long> d_acc;       // 4 result words + 8 debug counters
+    DevArray<uint32_t> d_fail;                // [0] count, [1..] list
     uint32_t fail_cap = 0;
     uint64_t node_base = 0;
     bvg_tuning tun{};
-    void* slow_ws = nullptr; uint64_t slow_ws_bytes = 0;   // tier-2 (global-memory) pools, kept between calls
+    DevWorkspace slow_ws;                     // tier-2 (global-memory) pools, kept between calls
     // predicted tiers run concurrently with tier 0 on high-priority side streams (their few, long blocks are the critical path)
     static constexpr int kSide = 5;            // [0] giants (global-memory kernel), [1..4] one per LDS size class
     hipStream_t side[kSide] = {}; hipEvent_t side_ev[kSide] = {};
-    void* giant_ws = nullptr; uint64_t giant_ws_bytes = 0; uint32_t* d_gslots = nullptr;   // work areas of the giant kernel: kGiantSlots slots + their busy flags
-    void* flow_ws = nullptr; size_t flow_ws_bytes = 0; uint32_t flow_waves = 0;   // scratch of the flow scan kernel (bvg_flow.hip): one slice per resident wavefront
-    void* dr_ws = nullptr; size_t dr_ws_bytes = 0;   // bvg_decode_range / bvg_successors_batch workspace, kept between calls (grown on demand)
-    void* tr_ws = nullptr; size_t tr_ws_bytes = 0;   // bvg_transpose workspace, kept between calls
+    DevWorkspace giant_ws; DevArray<uint32_t> d_gslots;   // work areas of the giant kernel: kGiantSlots slots + their busy flags
+    DevWorkspace flow_ws; uint32_t flow_waves = 0;   // scratch of the flow scan kernel (bvg_flow.hip): one slice per resident wavefront
+    DevWorkspace dr_ws;                       // bvg_decode_range / bvg_successors_batch workspace, kept between calls (grown on demand)
+    DevWorkspace tr_ws;                       // bvg_transpose workspace, kept between calls
     size_t tr_o_cum = 0, tr_o_succ = 0;             // where the last transpose left the graph's own CSR in it (bvg_symmetrize)
     int skip_mode = 0; uint32_t* skip_cnt = nullptr;   // transient: set while this handle builds the skip index
     std::shared_ptr<SkipIndex> skip_building;          // transient: the index the fill pass (skip_mode 2) writes
     struct Pred {
         // the work lists, one after another in d_lists: the row kernel's tier 0 and LDS classes 1-4, giants, the generic kernel, the lean scan kernel's tier 0 and classes 1-4
         enum Slot : int { kRow0, kRowC1, kRowC2, kRowC3, kRowC4, kGiant, kGeneric, kLean0, kLeanC1, kLeanC2, kLeanC3, kLeanC4, kSlots };
-        uint64_t plan_version = 0, skip_gen = 0; uint32_t lo = 0, n = 0, pool0 = 0, mode = 0; uint32_t* d_lists = nullptr; uint32_t count[kSlots] = {}; uint64_t giant_need = 0;
+        uint64_t plan_version = 0, skip_gen = 0; uint32_t lo = 0, n = 0, pool0 = 0, mode = 0; DevArray<uint32_t> d_lists; uint32_t count[kSlots] = {}; uint64_t giant_need = 0;
         size_t offset(int slot) const { size_t o = 0; for (int c = 0; c < slot; c++) o += count[c]; return o; }   // of the slot's list in d_lists
         std::vector<uint8_t> learned; std::vector<uint8_t> leanfail; uint64_t learned_version = 0, learned_gen = 0; uint32_t learned_pool0 = 0, learned_mode = 0; bool dirty = false;   // tier in which a mispredicted block finally succeeded: the next scans send it there directly
     } pred2[2];                                      // [0] scans, [1] materialising calls (round 6: a handle that alternates bvg_scan and bvg_decode_range keeps what it learned for each; one slot made every change of mode start from the prediction again)
+    bvg_graph() = default; bvg_graph(const bvg_graph&) = delete; bvg_graph& operator=(const bvg_graph&) = delete;
+    ~bvg_graph() {                                   // (the streams first; the arrays and workspaces above free themselves after it)
+        if (sh) (void)hipSetDevice(sh->device);
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        for (int i = 0; i < kSide; i++) { if (side[i]) { (void)hipStreamSynchronize(side[i]); (void)hipStreamDestroy(side[i]); } if (side_ev[i]) (void)hipEventDestroy(side_ev[i]); }
+    }
 };
 
 namespace bvghost {
@@ -209,13 +255,13 @@ struct HostBits {
     uint64_t delta() { uint64_t m = gamma(); if (m > 63) { eof = true; return 0; } return ((1ull << m) | bits((unsigned)m)) - 1; }
 };
 
-struct PackedOffsets { uint32_t* lo; uint64_t* hi; };   // bvg_tile hands over an index it wrote in packed form
+struct PackedOffsets { DevArray<uint32_t> lo; DevArray<uint64_t> hi; };   // bvg_tile hands over an index it wrote in packed form: open_common takes the arrays out of it
 
 // ---- bvg_plan.hip
 uint64_t next_plan_version();
 uint32_t block_bits_of(const bvg_graph* g);
 int open_common(const bvg_params* p, const uint8_t* h_graph, const void* d_graph_in, uint64_t nbytes, const uint64_t* h_offsets,
-                const void* d_offsets_in, int device, bvg_graph** out, const PackedOffsets* packed = nullptr);
+                const void* d_offsets_in, int device, bvg_graph** out, PackedOffsets* packed = nullptr);
 Codings codings_of(const bvg_params& p);
 int check_params(const bvg_params& p);
 int read_file(const std::string& path, std::vector<uint8_t>& out);

@@ -317,7 +317,6 @@ __global__ void hb_centrality_kernel(int which, const float* sod, const float* s
 }  // namespace bvg
 
 using bvghost::Batch;
-using bvghost::DevBuf;
 
 namespace {
 
@@ -333,7 +332,7 @@ struct bvg_hyperball {
     bvg_graph* g = nullptr;                        // a bvg_copy() flyweight: own stream and workspaces
     int log2m = 0; uint32_t flags = 0; uint64_t seed = 0;
     int64_t n = 0, mod_words = 0;
-    DevBuf buf[2], mod[2], sod, sid, ctl, ws, out_ws;
+    DevArray<uint8_t> buf[2], ws; DevArray<uint32_t> mod[2]; DevArray<float> sod, sid; DevArray<unsigned long long> ctl;
     int cur = 0;                                   // buf[cur] / mod[cur]: the current counters and their modified bits
     bool inited = false;
     int64_t iteration = -1; uint64_t modified = 0; double relative_increment = 0;
@@ -354,15 +353,14 @@ int ensure_plan(bvg_hyperball* h) {
     bvghost::SweepPlan sp;
     rc = sp.build(g, per, true); if (rc) return rc;                              // every node has a counter to carry over and to count, its list empty or not
     sp.layout(((size_t)sp.maxn / 64 + 1) * 8);
-    if (h->ws.p) (void)hipFree(h->ws.release());
     if (h->ws.alloc(sp.bytes)) return BVG_E_NOMEM;                               // counters + the largest batch: does not fit
-    sp.bind(h->ws.p);
+    sp.bind(h->ws.get());
     h->sweep = std::move(sp); h->planned = true;
     return 0;
 }
 
 template <int LOG2M> void launch_init(bvg_hyperball* h) {
-    hipLaunchKernelGGL((hb_init_kernel<LOG2M>), dim3(grid(h->n * (int64_t)((1 << LOG2M) / 16), 256)), dim3(256), 0, h->g->stream, (uint8_t*)h->buf[h->cur].p, h->n, h->seed);
+    hipLaunchKernelGGL((hb_init_kernel<LOG2M>), dim3(grid(h->n * (int64_t)((1 << LOG2M) / 16), 256)), dim3(256), 0, h->g->stream, h->buf[h->cur].get(), h->n, h->seed);
 }
 template <int LOG2M> void launch_iterate(bvg_hyperball* h, const IterArgs& a) {
     hipLaunchKernelGGL((hb_iterate_kernel<LOG2M>), dim3(grid(a.cnt, 256)), dim3(256), 0, h->g->stream, a);
@@ -379,9 +377,9 @@ int init_impl(bvg_hyperball* h, uint64_t seed) {
     h->seed = seed; h->cur = 0; h->inited = false;
     if (h->n) {
         HB_DISPATCH(launch_init, h);
-        hipLaunchKernelGGL(hb_fill_mod_kernel, dim3(grid(h->mod_words, 256)), dim3(256), 0, g->stream, (uint32_t*)h->mod[0].p, h->n, h->mod_words);
-        if (h->sod.p) HIPCHK(hipMemsetAsync(h->sod.p, 0, (size_t)h->n * 4, g->stream));
-        if (h->sid.p) HIPCHK(hipMemsetAsync(h->sid.p, 0, (size_t)h->n * 4, g->stream));
+        hipLaunchKernelGGL(hb_fill_mod_kernel, dim3(grid(h->mod_words, 256)), dim3(256), 0, g->stream, h->mod[0].get(), h->n, h->mod_words);
+        if (h->sod.get()) HIPCHK(hipMemsetAsync(h->sod.get(), 0, (size_t)h->n * 4, g->stream));
+        if (h->sid.get()) HIPCHK(hipMemsetAsync(h->sid.get(), 0, (size_t)h->n * 4, g->stream));
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(g->stream));
@@ -398,11 +396,11 @@ int iterate_impl(bvg_hyperball* h) {
     const bool dbgt = dbg_on();
     Stopwatch sw;
     double t_dec = 0, t_it = 0;
-    unsigned long long* const ctl = (unsigned long long*)h->ctl.p;
+    unsigned long long* const ctl = h->ctl.get();
     double* const d_total = (double*)(ctl + kCtlWords);
     const int nxt = h->cur ^ 1;
     HIPCHK(hipMemsetAsync(ctl, 0, (kCtlWords + 1) * 8, g->stream));
-    HIPCHK(hipMemsetAsync(h->mod[nxt].p, 0, (size_t)h->mod_words * 4, g->stream));
+    HIPCHK(hipMemsetAsync(h->mod[nxt].get(), 0, (size_t)h->mod_words * 4, g->stream));
     const bvghost::SweepPlan& sp = h->sweep;
     double* const b_part = (double*)sp.extra();
     h->inited = false;                                                       // (an error below leaves half an iteration: init first)
@@ -413,9 +411,9 @@ int iterate_impl(bvg_hyperball* h) {
         if (dbgt) { HIPCHK(hipStreamSynchronize(g->stream)); t_dec += sw.lap(); }
         IterArgs a;
         a.cum = sp.cum(); a.succ = sp.succ(); a.lo = b.lo; a.cnt = cnt; a.n = h->n;
-        a.cur = (const uint8_t*)h->buf[h->cur].p; a.next = (uint8_t*)h->buf[nxt].p;
-        a.cur_mod = (const uint32_t*)h->mod[h->cur].p; a.next_mod = (uint32_t*)h->mod[nxt].p;
-        a.sod = (float*)h->sod.p; a.sid = (float*)h->sid.p; a.dist = (double)(h->iteration + 2);
+        a.cur = h->buf[h->cur].get(); a.next = h->buf[nxt].get();
+        a.cur_mod = h->mod[h->cur].get(); a.next_mod = h->mod[nxt].get();
+        a.sod = h->sod.get(); a.sid = h->sid.get(); a.dist = (double)(h->iteration + 2);
         a.alpha_mm = alpha_mm_of(h->log2m); a.partial = b_part; a.ctl = ctl;
         HB_DISPATCH(launch_iterate, h, a);
         hipLaunchKernelGGL(hb_reduce_kernel, dim3(1), dim3(256), 0, g->stream, (const double*)b_part, (cnt + 63) / 64, d_total);
@@ -444,9 +442,9 @@ int counts_impl(bvg_hyperball* h, int64_t from, int64_t to, double* out, bool de
     if (to == from) return 0;
     bvg_graph* g = h->g;
     double* d_out = out;
-    DevBuf tmp;
-    if (!dev) { if (tmp.alloc((size_t)(to - from) * 8)) return BVG_E_NOMEM; d_out = (double*)tmp.p; }
-    hipLaunchKernelGGL(hb_counts_kernel, dim3(grid(to - from, 256)), dim3(256), 0, g->stream, (const uint8_t*)h->buf[h->cur].p, from, to, h->log2m, alpha_mm_of(h->log2m), d_out);
+    DevArray<double> tmp;
+    if (!dev) { if (tmp.alloc((size_t)(to - from))) return BVG_E_NOMEM; d_out = tmp; }
+    hipLaunchKernelGGL(hb_counts_kernel, dim3(grid(to - from, 256)), dim3(256), 0, g->stream, h->buf[h->cur].get(), from, to, h->log2m, alpha_mm_of(h->log2m), d_out);
     HIPCHK(hipGetLastError());
     if (!dev) HIPCHK(hipMemcpyAsync(out, d_out, (size_t)(to - from) * 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
@@ -456,18 +454,18 @@ int counts_impl(bvg_hyperball* h, int64_t from, int64_t to, double* out, bool de
 int centrality_impl(bvg_hyperball* h, int which, float* out, bool dev) {
     if (which < BVG_HB_WHICH_SUM_OF_DISTANCES || which > BVG_HB_WHICH_REACHABLE || (!out && h->n)) return BVG_E_ARG;
     const bool need_sod = which == BVG_HB_WHICH_SUM_OF_DISTANCES || which == BVG_HB_WHICH_CLOSENESS || which == BVG_HB_WHICH_LIN || which == BVG_HB_WHICH_NIEMINEN;
-    if ((need_sod && !h->sod.p) || (which == BVG_HB_WHICH_HARMONIC && !h->sid.p) || !h->inited) return BVG_E_STATE;
+    if ((need_sod && !h->sod.get()) || (which == BVG_HB_WHICH_HARMONIC && !h->sid.get()) || !h->inited) return BVG_E_STATE;
     if (!h->n) return 0;
     bvg_graph* g = h->g;
     const bool need_count = which == BVG_HB_WHICH_LIN || which == BVG_HB_WHICH_NIEMINEN || which == BVG_HB_WHICH_REACHABLE;
-    DevBuf cnt, tmp;
+    DevArray<double> cnt; DevArray<float> tmp;
     if (need_count) {
-        if (cnt.alloc((size_t)h->n * 8)) return BVG_E_NOMEM;
-        const int rc = counts_impl(h, 0, h->n, (double*)cnt.p, true); if (rc) return rc;
+        if (cnt.alloc((size_t)h->n)) return BVG_E_NOMEM;
+        const int rc = counts_impl(h, 0, h->n, cnt.get(), true); if (rc) return rc;
     }
     float* d_out = out;
-    if (!dev) { if (tmp.alloc((size_t)h->n * 4)) return BVG_E_NOMEM; d_out = (float*)tmp.p; }
-    hipLaunchKernelGGL(hb_centrality_kernel, dim3(grid(h->n, 256)), dim3(256), 0, g->stream, which, (const float*)h->sod.p, (const float*)h->sid.p, (const double*)cnt.p, h->n, d_out);
+    if (!dev) { if (tmp.alloc((size_t)h->n)) return BVG_E_NOMEM; d_out = tmp; }
+    hipLaunchKernelGGL(hb_centrality_kernel, dim3(grid(h->n, 256)), dim3(256), 0, g->stream, which, h->sod.get(), h->sid.get(), cnt.get(), h->n, d_out);
     HIPCHK(hipGetLastError());
     if (!dev) HIPCHK(hipMemcpyAsync(out, d_out, (size_t)h->n * 4, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
@@ -491,9 +489,9 @@ int bvg_hyperball_create(bvg_graph* g, int log2m, uint32_t flags, uint64_t seed,
         h->n = g->sh->p.nodes;
         h->mod_words = (h->n + 31) / 32 + 3;                 // (a wavefront's 64 bits may reach into the third word from its first)
         const size_t bytes = (size_t)std::max<int64_t>(h->n, 1) << log2m;
-        if (h->buf[0].alloc(bytes) || h->buf[1].alloc(bytes) || h->mod[0].alloc((size_t)h->mod_words * 4) || h->mod[1].alloc((size_t)h->mod_words * 4) || h->ctl.alloc(256)) return BVG_E_NOMEM;
-        if ((flags & BVG_HB_SUM_OF_DISTANCES) && h->sod.alloc((size_t)std::max<int64_t>(h->n, 1) * 4)) return BVG_E_NOMEM;
-        if ((flags & BVG_HB_HARMONIC) && h->sid.alloc((size_t)std::max<int64_t>(h->n, 1) * 4)) return BVG_E_NOMEM;
+        if (h->buf[0].alloc(bytes) || h->buf[1].alloc(bytes) || h->mod[0].alloc((size_t)h->mod_words) || h->mod[1].alloc((size_t)h->mod_words) || h->ctl.alloc(32)) return BVG_E_NOMEM;
+        if ((flags & BVG_HB_SUM_OF_DISTANCES) && h->sod.alloc((size_t)std::max<int64_t>(h->n, 1))) return BVG_E_NOMEM;
+        if ((flags & BVG_HB_HARMONIC) && h->sid.alloc((size_t)std::max<int64_t>(h->n, 1))) return BVG_E_NOMEM;
         *out = h.release();
         return 0;
     });
@@ -538,7 +536,7 @@ int bvg_hyperball_registers(bvg_hyperball* h, int64_t from, int64_t to, uint8_t*
     if (!h || from < 0 || to < from || to > h->n || (!out && to > from)) return BVG_E_ARG;
     return on_device(h, [&]() -> int {
         if (!h->inited) return BVG_E_STATE;
-        if (to > from) HIPCHK(hipMemcpy(out, (const uint8_t*)h->buf[h->cur].p + ((size_t)from << h->log2m), (size_t)(to - from) << h->log2m, hipMemcpyDeviceToHost));
+        if (to > from) HIPCHK(hipMemcpy(out, h->buf[h->cur].get() + ((size_t)from << h->log2m), (size_t)(to - from) << h->log2m, hipMemcpyDeviceToHost));
         return 0;
     });
 }

@@ -79,23 +79,22 @@ int build_skip(bvg_graph* g, const std::shared_ptr<Plan>& plp, uint32_t blo, uin
                     cause == SkipIndex::kStream ? " (bvg_build_index() tries again)" : " and try again every 8th time");
         return 0;
     };
-    DevBuf cnt_d;
+    DevArray<uint32_t> cnt_d;
     const auto tb0 = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - tb0).count(); };
-    if (cnt_d.alloc((size_t)nblk * sizeof(uint32_t)) || hipMemset(cnt_d.p, 0, (size_t)nblk * sizeof(uint32_t)) != hipSuccess) return give_up(SkipIndex::kResources);
-    g->skip_mode = 1; g->skip_cnt = (uint32_t*)cnt_d.p; g->skip_building = ix;          // (the counting pass counts in the new index's granularity)
+    if (cnt_d.alloc(nblk) || hipMemset(cnt_d, 0, (size_t)nblk * sizeof(uint32_t)) != hipSuccess) return give_up(SkipIndex::kResources);
+    g->skip_mode = 1; g->skip_cnt = cnt_d; g->skip_building = ix;          // (the counting pass counts in the new index's granularity)
     int r = run_decode(g, nfrom, nto, false, nullptr, nullptr, nullptr, nullptr, nullptr, &plp);
     g->skip_mode = 0; g->skip_cnt = nullptr; g->skip_building.reset();
     const double t_count = since();
     std::vector<uint32_t> cnt(nblk);
-    if (!r && hipMemcpy(cnt.data(), cnt_d.p, (size_t)nblk * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) r = BVG_E_HIP;
+    if (!r && hipMemcpy(cnt.data(), cnt_d, (size_t)nblk * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) r = BVG_E_HIP;
     if (r) return give_up((r == BVG_E_HIP || r == BVG_E_NOMEM) ? SkipIndex::kResources : SkipIndex::kStream);   // a bad stream surfaces in the caller's own decode
     std::vector<uint64_t> first(nblk + 1, 0);
     for (uint32_t i = 0; i < nblk; i++) first[i + 1] = first[i] + ((i >= blo && i < bhi) ? cnt[i] : 0u);
     const uint64_t total = first[nblk];
-    if (hipMalloc(&ix->d_first, (size_t)(nblk + 1) * sizeof(uint64_t)) != hipSuccess || hipMalloc(&ix->d_bit, total * sizeof(uint16_t) + 16) != hipSuccess ||
-        hipMalloc(&ix->d_fmt, nblk) != hipSuccess || hipMemset(ix->d_fmt, 0, nblk) != hipSuccess ||
-        hipMalloc(&ix->d_val, total * (build_wide ? sizeof(uint64_t) : sizeof(uint32_t)) + 16) != hipSuccess) return give_up(SkipIndex::kResources);
+    if (ix->d_first.alloc((size_t)nblk + 1) || ix->d_bit.alloc(total + 8) || ix->d_fmt.alloc(nblk) || hipMemset(ix->d_fmt, 0, nblk) != hipSuccess ||
+        ix->d_val.alloc(total * (build_wide ? sizeof(uint64_t) : sizeof(uint32_t)) + 16)) return give_up(SkipIndex::kResources);   // (16 bytes behind the entries of either array)
     if (hipMemcpy(ix->d_first, first.data(), (size_t)(nblk + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) return give_up(SkipIndex::kResources);
     // (entries nobody fills -- the allotment of a block that ends in the generic kernel -- read as zero: an index, and its file, are reproducible)
     if (hipMemsetAsync(ix->d_bit, 0, total * sizeof(uint16_t) + 16, g->stream) != hipSuccess || hipMemsetAsync(ix->d_val, 0, total * (build_wide ? sizeof(uint64_t) : sizeof(uint32_t)) + 16, g->stream) != hipSuccess) return give_up(SkipIndex::kResources);
@@ -157,11 +156,11 @@ static const char kIndexMagic[8] = {'B', 'V', 'G', 'I', 'D', 'X', '2', 0};
 
 // position-keyed word hash of a device array (launch_hash_words), synchronous
 static int device_hash(bvg_graph* g, const void* d, uint64_t bytes, uint64_t* out) {
-    DevBuf acc;
-    if (acc.alloc(8)) return BVG_E_NOMEM;
-    HIPCHK(hipMemsetAsync(acc.p, 0, 8, g->stream));
-    if (bytes) launch_hash_words(d, bytes, (unsigned long long*)acc.p, g->stream);
-    HIPCHK(hipMemcpyAsync(out, acc.p, 8, hipMemcpyDeviceToHost, g->stream));
+    DevArray<unsigned long long> acc;
+    if (acc.alloc(1)) return BVG_E_NOMEM;
+    HIPCHK(hipMemsetAsync(acc, 0, 8, g->stream));
+    if (bytes) launch_hash_words(d, bytes, acc, g->stream);
+    HIPCHK(hipMemcpyAsync(out, acc, 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     return 0;
 }
@@ -280,7 +279,7 @@ int load_index_impl(bvg_graph* g, const char* path) {
     for (size_t i = 0; i < nb; i++) if (pl.h_first[i] >= pl.h_first[i + 1]) return BVG_E_IO;
     uint64_t acc = 0, part = 0;
     acc = fold_hash(acc, host_hash(pl.h_first.data(), (nb + 1) * 8), 1); acc = fold_hash(acc, host_hash(pl.h_maxd.data(), nb * 4), 2);
-    if (hipMalloc(&pl.d_first, (nb + 1) * 8) != hipSuccess || hipMalloc(&pl.d_halo, nb * 4) != hipSuccess || hipMalloc(&pl.d_mask, nb * 8) != hipSuccess) { (void)hipGetLastError(); return BVG_E_NOMEM; }
+    if (pl.d_first.alloc(nb + 1) || pl.d_halo.alloc(nb) || pl.d_mask.alloc(nb)) return BVG_E_NOMEM;
     HIPCHK(hipMemcpy(pl.d_first, pl.h_first.data(), (nb + 1) * 8, hipMemcpyHostToDevice));
     {   // halos: range-checked on the host on their way in (a halo reaches at most kMaxHalo nodes back -- kMaxHaloBig for windows > kMaxWindow, bvg_kernels.h --
         // and never before node 0)
@@ -307,8 +306,7 @@ int load_index_impl(bvg_graph* g, const char* path) {
         }
         acc = fold_hash(acc, host_hash(ix->h_first.data(), (nb + 1) * 8), 5); acc = fold_hash(acc, host_hash(ix->h_fmt.data(), nb), 6);
         const size_t vb = ix->wide ? 8 : 4;
-        if (hipMalloc(&ix->d_first, (nb + 1) * 8) != hipSuccess || hipMalloc(&ix->d_bit, (size_t)ix->total * 2 + 16) != hipSuccess || hipMalloc(&ix->d_fmt, nb) != hipSuccess ||
-            hipMalloc(&ix->d_val, (size_t)ix->total * vb + 16) != hipSuccess) { (void)hipGetLastError(); return BVG_E_NOMEM; }
+        if (ix->d_first.alloc(nb + 1) || ix->d_bit.alloc((size_t)ix->total + 8) || ix->d_fmt.alloc(nb) || ix->d_val.alloc((size_t)ix->total * vb + 16)) return BVG_E_NOMEM;
         HIPCHK(hipMemcpy(ix->d_first, ix->h_first.data(), (nb + 1) * 8, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(ix->d_fmt, ix->h_fmt.data(), nb, hipMemcpyHostToDevice));
         if (!get_dev(f, ix->d_bit, (size_t)ix->total * 2) || !get_dev(f, ix->d_val, (size_t)ix->total * vb)) return BVG_E_IO;

@@ -22,26 +22,25 @@
 #include <string>
 #include <vector>
 
-#include "bvg_kernels.h"
+#include "bvg_host.h"
 
 struct bvg_labels {
     int device = 0, kind = 0, width = 0;
     int64_t nodes = 0;
     uint64_t nbytes = 0, padded = 0;
-    uint8_t* d_stream = nullptr;
-    uint64_t* d_offsets = nullptr;
+    DevArray<uint8_t> d_stream;
+    DevArray<uint64_t> d_offsets;
     hipStream_t stream = nullptr;
-    unsigned* d_err = nullptr;
-    // workspace (grown on demand)
-    uint64_t* d_cum = nullptr; uint64_t* d_tmp = nullptr;
-    size_t deg_cap = 0, tmp_cap = 0;
+    DevArray<unsigned> d_err;
+    DevWorkspace cum_ws, tmp_ws;              // the prefix sums of a range and the scan's scratch (grown on demand)
+    ~bvg_labels() {
+        (void)hipSetDevice(device);
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+    }
 };
 
 namespace bvg {
 namespace {
-
-#define LCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { if (dbg_on()) fprintf(stderr, "[bvg] %s -> %s (%s:%d)\n", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-                        return _e == hipErrorOutOfMemory ? BVG_E_NOMEM : BVG_E_HIP; } } while (0)
 
 __global__ void __launch_bounds__(256) labels_kernel(const uint8_t* stream, uint64_t limit_byte, const uint64_t* loff, int64_t from, int64_t count,
                                                      const int32_t* deg, const uint64_t* cum, int kind, int width, int32_t* out, unsigned* err) {
@@ -114,7 +113,7 @@ using namespace bvg;
 template <typename V> int labels_lists_impl(bvg_labels* l, int want_kind, int64_t from, int64_t to, const int32_t* outdeg, uint64_t* list_off, V* values, uint64_t cap, uint64_t* n_values) {
     if (!l || from < 0 || to < from || to > l->nodes || (to > from && !outdeg) || !list_off) return BVG_E_ARG;
     if (l->kind != want_kind) return BVG_E_UNSUPPORTED;
-    LCHK(hipSetDevice(l->device));
+    HIPCHK(hipSetDevice(l->device));
     const int64_t cnt = to - from;
     if (n_values) *n_values = 0;
     list_off[0] = 0;
@@ -122,33 +121,33 @@ template <typename V> int labels_lists_impl(bvg_labels* l, int want_kind, int64_
     uint64_t arcs = 0;
     for (int64_t i = 0; i < cnt; i++) { if (outdeg[i] < 0) return BVG_E_ARG; arcs += (uint64_t)outdeg[i]; }
     if (arcs == 0) return 0;
-    int32_t* d_deg = nullptr; int32_t* d_lens = nullptr; V* d_vals = nullptr; uint64_t* d_cum = nullptr; uint64_t* d_voff = nullptr; uint64_t* d_tmp = nullptr;
-    auto done = [&](int code) { for (void* p : {(void*)d_deg, (void*)d_lens, (void*)d_vals, (void*)d_cum, (void*)d_voff, (void*)d_tmp}) if (p) (void)hipFree(p); return code; };
+    DevArray<int32_t> deg_o, lens_o; DevArray<V> vals_o; DevArray<uint64_t> cum_o, voff_o, tmp_o;
     const size_t tneed = std::max(scan_tmp_elems(cnt), scan_tmp_elems((int64_t)arcs));
-    if (hipMalloc(&d_deg, (size_t)cnt * 4) != hipSuccess || hipMalloc(&d_cum, (size_t)(cnt + 1) * 8) != hipSuccess || hipMalloc(&d_lens, (size_t)arcs * 4) != hipSuccess ||
-        hipMalloc(&d_voff, (size_t)(arcs + 1) * 8) != hipSuccess || hipMalloc(&d_tmp, tneed * 8) != hipSuccess) return done(BVG_E_NOMEM);
-    if (hipMemcpy(d_deg, outdeg, (size_t)cnt * 4, hipMemcpyHostToDevice) != hipSuccess) return done(BVG_E_HIP);
+    if (deg_o.alloc((size_t)cnt) || cum_o.alloc((size_t)cnt + 1) || lens_o.alloc((size_t)arcs) || voff_o.alloc((size_t)arcs + 1) || tmp_o.alloc(tneed)) return BVG_E_NOMEM;
+    int32_t* const d_deg = deg_o; int32_t* const d_lens = lens_o; uint64_t* const d_cum = cum_o; uint64_t* const d_voff = voff_o; uint64_t* const d_tmp = tmp_o;
+    if (hipMemcpy(d_deg, outdeg, (size_t)cnt * 4, hipMemcpyHostToDevice) != hipSuccess) return BVG_E_HIP;
     launch_exclusive_scan(d_deg, d_cum, cnt, d_tmp, l->stream);
-    if (hipMemsetAsync(l->d_err, 0, sizeof(unsigned), l->stream) != hipSuccess) return done(BVG_E_HIP);
+    if (hipMemsetAsync(l->d_err, 0, sizeof(unsigned), l->stream) != hipSuccess) return BVG_E_HIP;
     const uint64_t limit = l->padded - 16;
     const dim3 grid((unsigned)((cnt + 255) / 256));
-    hipLaunchKernelGGL((label_lists_kernel<0, V>), grid, dim3(256), 0, l->stream, l->d_stream, limit, l->d_offsets, from, cnt, d_deg, d_cum, l->width, d_lens, (const uint64_t*)nullptr, (V*)nullptr, l->d_err);
+    hipLaunchKernelGGL((label_lists_kernel<0, V>), grid, dim3(256), 0, l->stream, l->d_stream.get(), limit, l->d_offsets.get(), from, cnt, d_deg, d_cum, l->width, d_lens, (const uint64_t*)nullptr, (V*)nullptr, l->d_err.get());
     launch_exclusive_scan(d_lens, d_voff, (int64_t)arcs, d_tmp, l->stream);
     unsigned herr = 0;
-    if (hipMemcpyAsync(&herr, l->d_err, sizeof(unsigned), hipMemcpyDeviceToHost, l->stream) != hipSuccess) return done(BVG_E_HIP);
-    if (hipMemcpyAsync(list_off, d_voff, (size_t)(arcs + 1) * 8, hipMemcpyDeviceToHost, l->stream) != hipSuccess) return done(BVG_E_HIP);
-    if (hipStreamSynchronize(l->stream) != hipSuccess) return done(BVG_E_HIP);
-    if (herr) return done(BVG_E_EOF);
+    if (hipMemcpyAsync(&herr, l->d_err, sizeof(unsigned), hipMemcpyDeviceToHost, l->stream) != hipSuccess) return BVG_E_HIP;
+    if (hipMemcpyAsync(list_off, d_voff, (size_t)(arcs + 1) * 8, hipMemcpyDeviceToHost, l->stream) != hipSuccess) return BVG_E_HIP;
+    if (hipStreamSynchronize(l->stream) != hipSuccess) return BVG_E_HIP;
+    if (herr) return BVG_E_EOF;
     const uint64_t total = list_off[arcs];
     if (n_values) *n_values = total;
-    if (total > cap || (total && !values)) return done(BVG_E_CAPACITY);
-    if (total == 0) return done(0);
-    if (hipMalloc(&d_vals, (size_t)total * sizeof(V)) != hipSuccess) return done(BVG_E_NOMEM);
-    hipLaunchKernelGGL((label_lists_kernel<1, V>), grid, dim3(256), 0, l->stream, l->d_stream, limit, l->d_offsets, from, cnt, d_deg, d_cum, l->width, (int32_t*)nullptr, d_voff, d_vals, l->d_err);
-    if (hipMemcpyAsync(values, d_vals, (size_t)total * sizeof(V), hipMemcpyDeviceToHost, l->stream) != hipSuccess) return done(BVG_E_HIP);
-    if (hipMemcpyAsync(&herr, l->d_err, sizeof(unsigned), hipMemcpyDeviceToHost, l->stream) != hipSuccess) return done(BVG_E_HIP);
-    if (hipStreamSynchronize(l->stream) != hipSuccess) return done(BVG_E_HIP);
-    return done(herr ? BVG_E_EOF : 0);
+    if (total > cap || (total && !values)) return BVG_E_CAPACITY;
+    if (total == 0) return 0;
+    if (vals_o.alloc((size_t)total)) return BVG_E_NOMEM;
+    V* const d_vals = vals_o;
+    hipLaunchKernelGGL((label_lists_kernel<1, V>), grid, dim3(256), 0, l->stream, l->d_stream.get(), limit, l->d_offsets.get(), from, cnt, d_deg, d_cum, l->width, (int32_t*)nullptr, d_voff, d_vals, l->d_err.get());
+    if (hipMemcpyAsync(values, d_vals, (size_t)total * sizeof(V), hipMemcpyDeviceToHost, l->stream) != hipSuccess) return BVG_E_HIP;
+    if (hipMemcpyAsync(&herr, l->d_err, sizeof(unsigned), hipMemcpyDeviceToHost, l->stream) != hipSuccess) return BVG_E_HIP;
+    if (hipStreamSynchronize(l->stream) != hipSuccess) return BVG_E_HIP;
+    return herr ? BVG_E_EOF : 0;
 }
 
 extern "C" {
@@ -200,19 +199,18 @@ int bvg_labels_open_mem(int kind, int width, int64_t nodes, const uint8_t* strea
     for (int64_t i = 0; i < nodes; i++) if (label_offsets[i] > label_offsets[i + 1]) return BVG_E_IO;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return BVG_E_HIP;
-    LCHK(hipSetDevice(device));
-    bvg_labels* l = new bvg_labels();
+    HIPCHK(hipSetDevice(device));
+    std::unique_ptr<bvg_labels> l(new bvg_labels());
     l->device = device; l->kind = kind; l->width = width; l->nodes = nodes; l->nbytes = nbytes;
     l->padded = ((nbytes + 15) & ~15ull) + 16;
-    auto fail = [&](int code) { bvg_labels_close(l); return code; };
-    if (hipMalloc(&l->d_stream, l->padded) != hipSuccess) return fail(BVG_E_NOMEM);
-    if (hipMemset(l->d_stream, 0, l->padded) != hipSuccess) return fail(BVG_E_HIP);
-    if (nbytes && hipMemcpy(l->d_stream, stream, nbytes, hipMemcpyHostToDevice) != hipSuccess) return fail(BVG_E_HIP);
-    if (hipMalloc(&l->d_offsets, (size_t)(nodes + 1) * sizeof(uint64_t)) != hipSuccess) return fail(BVG_E_NOMEM);
-    if (hipMemcpy(l->d_offsets, label_offsets, (size_t)(nodes + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) return fail(BVG_E_HIP);
-    if (hipMalloc(&l->d_err, sizeof(unsigned)) != hipSuccess) return fail(BVG_E_NOMEM);
-    if (hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking) != hipSuccess) return fail(BVG_E_HIP);
-    *out = l;
+    if (l->d_stream.alloc(l->padded)) return BVG_E_NOMEM;
+    if (hipMemset(l->d_stream, 0, l->padded) != hipSuccess) return BVG_E_HIP;
+    if (nbytes && hipMemcpy(l->d_stream, stream, nbytes, hipMemcpyHostToDevice) != hipSuccess) return BVG_E_HIP;
+    if (l->d_offsets.alloc((size_t)nodes + 1)) return BVG_E_NOMEM;
+    if (hipMemcpy(l->d_offsets, label_offsets, (size_t)(nodes + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) return BVG_E_HIP;
+    if (l->d_err.alloc(1)) return BVG_E_NOMEM;
+    if (hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking) != hipSuccess) return BVG_E_HIP;
+    *out = l.release();
     return 0;
 }
 
@@ -265,13 +263,7 @@ int bvg_labels_open(const char* basename, int64_t nodes, int device, bvg_labels*
     return bvg_labels_open_mem(kind, width, nodes, lab.data(), lab.size(), lo.data(), device, out);
 }
 
-void bvg_labels_close(bvg_labels* l) {
-    if (!l) return;
-    (void)hipSetDevice(l->device);
-    if (l->stream) { (void)hipStreamSynchronize(l->stream); (void)hipStreamDestroy(l->stream); }
-    for (void* p : {(void*)l->d_stream, (void*)l->d_offsets, (void*)l->d_err, (void*)l->d_cum, (void*)l->d_tmp}) if (p) (void)hipFree(p);
-    delete l;
-}
+void bvg_labels_close(bvg_labels* l) { delete l; }
 
 int bvg_labels_info(const bvg_labels* l, int* kind, int* width, int64_t* nodes, uint64_t* stream_bytes) {
     if (!l) return BVG_E_ARG;
@@ -287,36 +279,25 @@ int bvg_labels_info(const bvg_labels* l, int* kind, int* width, int64_t* nodes, 
 int bvg_labels_decode_range_dev(bvg_labels* l, int64_t from, int64_t to, const void* d_outdeg, void* d_labels, uint64_t cap, uint64_t* n_labels) {
     if (!l || from < 0 || to < from || to > l->nodes || (to > from && !d_outdeg)) return BVG_E_ARG;
     if (l->kind == BVG_LABEL_FIXED_INT_LIST || l->kind == BVG_LABEL_FIXED_LONG_LIST) return BVG_E_UNSUPPORTED;   // use bvg_labels_decode_range_lists[64]
-    LCHK(hipSetDevice(l->device));
+    HIPCHK(hipSetDevice(l->device));
     const int64_t cnt = to - from;
     if (n_labels) *n_labels = 0;
     if (cnt == 0) return 0;
-    if ((size_t)(cnt + 1) > l->deg_cap) {
-        if (l->d_cum) { (void)hipFree(l->d_cum); l->d_cum = nullptr; }
-        l->deg_cap = 0;
-        LCHK(hipMalloc(&l->d_cum, (size_t)(cnt + 1) * sizeof(uint64_t)));
-        l->deg_cap = (size_t)(cnt + 1);
-    }
-    const size_t tneed = scan_tmp_elems(cnt);
-    if (tneed > l->tmp_cap) {
-        if (l->d_tmp) { (void)hipFree(l->d_tmp); l->d_tmp = nullptr; }
-        l->tmp_cap = 0;
-        LCHK(hipMalloc(&l->d_tmp, tneed * sizeof(uint64_t)));
-        l->tmp_cap = tneed;
-    }
-    launch_exclusive_scan(static_cast<const int32_t*>(d_outdeg), l->d_cum, cnt, l->d_tmp, l->stream);
+    if (l->cum_ws.reserve((size_t)(cnt + 1) * sizeof(uint64_t)) || l->tmp_ws.reserve(scan_tmp_elems(cnt) * sizeof(uint64_t))) return BVG_E_NOMEM;
+    uint64_t* const d_cum = (uint64_t*)l->cum_ws.get();
+    launch_exclusive_scan(static_cast<const int32_t*>(d_outdeg), d_cum, cnt, (uint64_t*)l->tmp_ws.get(), l->stream);
     uint64_t total = 0;
-    LCHK(hipMemcpyAsync(&total, l->d_cum + cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, l->stream));
-    LCHK(hipStreamSynchronize(l->stream));
+    HIPCHK(hipMemcpyAsync(&total, d_cum + cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, l->stream));
+    HIPCHK(hipStreamSynchronize(l->stream));
     if (n_labels) *n_labels = total;
     if (total > cap || (total && !d_labels)) return BVG_E_CAPACITY;
-    LCHK(hipMemsetAsync(l->d_err, 0, sizeof(unsigned), l->stream));
+    HIPCHK(hipMemsetAsync(l->d_err, 0, sizeof(unsigned), l->stream));
     const uint64_t limit = l->padded - 16;
-    hipLaunchKernelGGL(labels_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, l->stream, l->d_stream, limit, l->d_offsets, from, cnt,
-                       static_cast<const int32_t*>(d_outdeg), l->d_cum, l->kind, l->width, static_cast<int32_t*>(d_labels), l->d_err);
+    hipLaunchKernelGGL(labels_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, l->stream, l->d_stream.get(), limit, l->d_offsets.get(), from, cnt,
+                       static_cast<const int32_t*>(d_outdeg), d_cum, l->kind, l->width, static_cast<int32_t*>(d_labels), l->d_err.get());
     unsigned herr = 0;
-    LCHK(hipMemcpyAsync(&herr, l->d_err, sizeof(unsigned), hipMemcpyDeviceToHost, l->stream));
-    LCHK(hipStreamSynchronize(l->stream));
+    HIPCHK(hipMemcpyAsync(&herr, l->d_err, sizeof(unsigned), hipMemcpyDeviceToHost, l->stream));
+    HIPCHK(hipStreamSynchronize(l->stream));
     if (herr) return BVG_E_EOF;                                               // the degrees do not match the label stream
     return 0;
 }
@@ -324,7 +305,7 @@ int bvg_labels_decode_range_dev(bvg_labels* l, int64_t from, int64_t to, const v
 // Same with host buffers: outdeg[to-from] as returned by bvg_decode_range, labels[cap].
 int bvg_labels_decode_range(bvg_labels* l, int64_t from, int64_t to, const int32_t* outdeg, int32_t* labels, uint64_t cap, uint64_t* n_labels) {
     if (!l || from < 0 || to < from || to > l->nodes || (to > from && !outdeg)) return BVG_E_ARG;
-    LCHK(hipSetDevice(l->device));
+    HIPCHK(hipSetDevice(l->device));
     const int64_t cnt = to - from;
     if (n_labels) *n_labels = 0;
     if (cnt == 0) return 0;
@@ -332,16 +313,14 @@ int bvg_labels_decode_range(bvg_labels* l, int64_t from, int64_t to, const int32
     for (int64_t i = 0; i < cnt; i++) { if (outdeg[i] < 0) return BVG_E_ARG; total += (uint64_t)outdeg[i]; }
     if (n_labels) *n_labels = total;
     if (total > cap || (total && !labels)) return BVG_E_CAPACITY;
-    int32_t* d_deg = nullptr; int32_t* d_lab = nullptr;
-    LCHK(hipMalloc(&d_deg, (size_t)cnt * sizeof(int32_t)));
-    if (hipMalloc(&d_lab, (size_t)(total ? total : 1) * sizeof(int32_t)) != hipSuccess) { (void)hipFree(d_deg); return BVG_E_NOMEM; }
+    DevArray<int32_t> d_deg, d_lab;
+    if (d_deg.alloc((size_t)cnt) || d_lab.alloc((size_t)total)) return BVG_E_NOMEM;
     int r = BVG_E_HIP;
     if (hipMemcpy(d_deg, outdeg, (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess) {
         uint64_t n2 = 0;
         r = bvg_labels_decode_range_dev(l, from, to, d_deg, d_lab, total, &n2);
         if (r == 0 && total && hipMemcpy(labels, d_lab, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) r = BVG_E_HIP;
     }
-    (void)hipFree(d_lab); (void)hipFree(d_deg);
     return r;
 }
 

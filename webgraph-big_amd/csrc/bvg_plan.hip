@@ -41,7 +41,7 @@ int read_file(const std::string& path, std::vector<uint8_t>& out) {
 }
 
 int make_handle(Shared* sh, bvg_graph** out) {
-    bvg_graph* g = new bvg_graph();
+    std::unique_ptr<bvg_graph> g(new bvg_graph());          // (a handle that fails half-way is deleted: its streams, events and arrays with it)
     g->sh = sh;
     HIPCHK(hipSetDevice(sh->device));
     HIPCHK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
@@ -55,22 +55,14 @@ int make_handle(Shared* sh, bvg_graph** out) {
     }
     HIPCHK(hipEventCreate(&g->ev0));
     HIPCHK(hipEventCreate(&g->ev1));
-    HIPCHK(hipMalloc(&g->d_acc, (size_t)kAccStripes * kAccStride * sizeof(unsigned long long)));   // stripe 0 also holds the debug counters [4..19]
     g->fail_cap = 1u << 16;
-    HIPCHK(hipMalloc(&g->d_fail, (2 * (size_t)g->fail_cap + 1) * sizeof(uint32_t)));
-    *out = g;
+    if (g->d_acc.alloc((size_t)kAccStripes * kAccStride) || g->d_fail.alloc(2 * (size_t)g->fail_cap + 1)) return BVG_E_NOMEM;   // stripe 0 of d_acc also holds the debug counters [4..19]
+    *out = g.release();
     return 0;
 }
 
 void release_shared(Shared* sh) {
-    if (sh->refs.fetch_sub(1) != 1) return;
-    (void)hipSetDevice(sh->device);
-    sh->plans.clear();
-    if (sh->own_graph && sh->d_graph) (void)hipFree(sh->d_graph);
-    if (sh->d_off_lo) (void)hipFree(sh->d_off_lo);
-    if (sh->d_off_hi) (void)hipFree(sh->d_off_hi);
-    if (sh->own_wide && sh->d_off_wide) (void)hipFree(sh->d_off_wide);
-    delete sh;
+    if (sh->refs.fetch_sub(1) == 1) delete sh;
 }
 
 int ensure_device(int device) {
@@ -102,13 +94,14 @@ int build_plan(bvg_graph* g, uint32_t block_bits, std::shared_ptr<Plan>& out) {
     uint64_t nb = (sh->total_bits + block_bits - 1) / block_bits;
     if (nb == 0) nb = 1;
     if (nb > 0x7FFFFFF0ull) return BVG_E_UNSUPPORTED;
-    uint64_t* d_first0 = nullptr;
-    HIPCHK(hipMalloc(&d_first0, (nb + 1) * sizeof(uint64_t)));
-    launch_plan_boundaries(sh->offs, n, block_bits, nb, d_first0, g->stream);
     std::vector<uint64_t> first(nb + 1);
-    HIPCHK(hipMemcpyAsync(first.data(), d_first0, (nb + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
-    (void)hipFree(d_first0);
+    {
+        DevArray<uint64_t> d_first0;
+        if (d_first0.alloc(nb + 1)) return BVG_E_NOMEM;
+        launch_plan_boundaries(sh->offs, n, block_bits, nb, d_first0, g->stream);
+        HIPCHK(hipMemcpyAsync(first.data(), d_first0, (nb + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipStreamSynchronize(g->stream));
+    }
     // drop empty blocks (a record longer than block_bits spans several targets)
     first[0] = 0;
     std::vector<uint64_t> uniq; uniq.reserve(first.size());
@@ -120,15 +113,15 @@ int build_plan(bvg_graph* g, uint32_t block_bits, std::shared_ptr<Plan>& out) {
     // run: 157 k such blocks = 2.0 s of a scan whose tier 0 ends after 1.2 s).  Cut the block in front of the long record (it is the
     // block's last node or nearly: the record runs past the block's end), so that the nodes before it stay with the LDS kernels.
     if (!knob("BVG_NO_LONGCUT")) {
-        uint64_t *d_f = nullptr, *d_node = nullptr, *d_bits = nullptr;
-        HIPCHK(hipMalloc(&d_f, (nblk + 1) * sizeof(uint64_t))); HIPCHK(hipMalloc(&d_node, (size_t)nblk * sizeof(uint64_t))); HIPCHK(hipMalloc(&d_bits, (size_t)nblk * sizeof(uint64_t)));
+        DevArray<uint64_t> d_f, d_node, d_bits;
+        if (d_f.alloc((size_t)nblk + 1) || d_node.alloc(nblk) || d_bits.alloc(nblk)) return BVG_E_NOMEM;
         HIPCHK(hipMemcpyAsync(d_f, uniq.data(), (nblk + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, g->stream));
         launch_plan_longest(sh->offs, d_f, nblk, d_node, d_bits, g->stream);
         std::vector<uint64_t> hn(nblk), hb(nblk);
         HIPCHK(hipMemcpyAsync(hn.data(), d_node, (size_t)nblk * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
         HIPCHK(hipMemcpyAsync(hb.data(), d_bits, (size_t)nblk * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream));
         HIPCHK(hipStreamSynchronize(g->stream));
-        (void)hipFree(d_f); (void)hipFree(d_node); (void)hipFree(d_bits);
+        d_f.reset(); d_node.reset(); d_bits.reset();
         std::vector<uint64_t> cut; cut.reserve(uniq.size() + 1024);
         for (uint32_t k = 0; k < nblk; k++) {
             cut.push_back(uniq[k]);
@@ -145,10 +138,8 @@ int build_plan(bvg_graph* g, uint32_t block_bits, std::shared_ptr<Plan>& out) {
     for (int round = 0; round < 2; round++) {
       bool done = false;
       for (int pass = 0; pass < 2 && !done; pass++) {
-        uint64_t* d_first = nullptr; uint32_t* d_halo = nullptr; uint64_t* d_mask = nullptr;
-        HIPCHK(hipMalloc(&d_first, (nblk + 1) * sizeof(uint64_t)));
-        HIPCHK(hipMalloc(&d_halo, (size_t)nblk * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&d_mask, (size_t)nblk * sizeof(uint64_t)));
+        DevArray<uint64_t> d_first, d_mask; DevArray<uint32_t> d_halo;
+        if (d_first.alloc((size_t)nblk + 1) || d_halo.alloc(nblk) || d_mask.alloc(nblk)) return BVG_E_NOMEM;
         HIPCHK(hipMemcpyAsync(d_first, uniq.data(), (nblk + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, g->stream));
         launch_plan_halo(sh->d_graph, limit, sh->offs, n, d_first, nblk, sh->p.window_size, codings_of(sh->p), d_halo, d_mask, g->stream);
         std::vector<uint32_t> halo(nblk);
@@ -157,20 +148,20 @@ int build_plan(bvg_graph* g, uint32_t block_bits, std::shared_ptr<Plan>& out) {
         bool any_bad = false;
         for (uint32_t k = 0; k < nblk; k++) if (halo[k] == 0xFFFFFFFFu) { any_bad = true; break; }
         if (!any_bad || pass == 1) {
-            if (any_bad) { (void)hipFree(d_first); (void)hipFree(d_halo); (void)hipFree(d_mask); return BVG_E_UNSUPPORTED; }
+            if (any_bad) return BVG_E_UNSUPPORTED;
             // per-block largest "list + window" (one wavefront per block), kept on the host to predict tiers; the block's longest list and its node
-            uint32_t* d_maxd = nullptr; uint64_t* d_bign = nullptr; uint32_t* d_bigd = nullptr;
-            HIPCHK(hipMalloc(&d_maxd, (size_t)nblk * sizeof(uint32_t)));
             const bool want_cuts = refine && round == 0;
-            if (want_cuts) { HIPCHK(hipMalloc(&d_bign, (size_t)nblk * sizeof(uint64_t))); HIPCHK(hipMalloc(&d_bigd, (size_t)nblk * sizeof(uint32_t))); }
-            launch_plan_maxd(sh->d_graph, limit, sh->offs, d_first, d_halo, nblk, sh->p.outdegree_coding, sh->p.window_size, d_maxd, d_bign, d_bigd, g->stream);
             std::vector<uint32_t> maxd(nblk), bigd(want_cuts ? nblk : 0); std::vector<uint64_t> bign(want_cuts ? nblk : 0);
-            hipError_t e2 = hipMemcpyAsync(maxd.data(), d_maxd, (size_t)nblk * sizeof(uint32_t), hipMemcpyDeviceToHost, g->stream);
-            if (e2 == hipSuccess && want_cuts) e2 = hipMemcpyAsync(bign.data(), d_bign, (size_t)nblk * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
-            if (e2 == hipSuccess && want_cuts) e2 = hipMemcpyAsync(bigd.data(), d_bigd, (size_t)nblk * sizeof(uint32_t), hipMemcpyDeviceToHost, g->stream);
-            if (e2 == hipSuccess) e2 = hipStreamSynchronize(g->stream);
-            (void)hipFree(d_maxd); if (d_bign) (void)hipFree(d_bign); if (d_bigd) (void)hipFree(d_bigd);
-            if (e2 != hipSuccess) { (void)hipFree(d_first); (void)hipFree(d_halo); (void)hipFree(d_mask); return BVG_E_HIP; }
+            {
+                DevArray<uint32_t> d_maxd, d_bigd; DevArray<uint64_t> d_bign;      // (the last two stay null without cuts)
+                if (d_maxd.alloc(nblk) || (want_cuts && (d_bign.alloc(nblk) || d_bigd.alloc(nblk)))) return BVG_E_NOMEM;
+                launch_plan_maxd(sh->d_graph, limit, sh->offs, d_first, d_halo, nblk, sh->p.outdegree_coding, sh->p.window_size, d_maxd, d_bign, d_bigd, g->stream);
+                hipError_t e2 = hipMemcpyAsync(maxd.data(), d_maxd, (size_t)nblk * sizeof(uint32_t), hipMemcpyDeviceToHost, g->stream);
+                if (e2 == hipSuccess && want_cuts) e2 = hipMemcpyAsync(bign.data(), d_bign, (size_t)nblk * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
+                if (e2 == hipSuccess && want_cuts) e2 = hipMemcpyAsync(bigd.data(), d_bigd, (size_t)nblk * sizeof(uint32_t), hipMemcpyDeviceToHost, g->stream);
+                if (e2 == hipSuccess) e2 = hipStreamSynchronize(g->stream);
+                if (e2 != hipSuccess) return BVG_E_HIP;
+            }
             if (want_cuts) {
                 // a block above the tier-0 capacity (about 2 000 elements of "worst list + window" / 2) with one list that is most of it
                 const uint64_t W1 = knob("BVG_LISTCUT_BEHIND") ? (uint64_t)atoi(knob("BVG_LISTCUT_BEHIND")) : 2 * (uint64_t)sh->p.window_size + 1;   // (behind the list: W + 1 would do for the nodes that copy from it, but chains through them reach back as well: 8 / 15 / 22 nodes measured 251 / 255 / 254 G edges/s)
@@ -186,7 +177,6 @@ int build_plan(bvg_graph* g, uint32_t block_bits, std::shared_ptr<Plan>& out) {
                 cut.push_back(uniq[nblk]);
                 if (ncut && cut.size() - 1 <= 0x7FFFFFF0ull) {
                     if (dbg_on()) fprintf(stderr, "[bvg] plan: %zu cuts around large lists (%u blocks before)\n", ncut, nblk);
-                    (void)hipFree(d_first); (void)hipFree(d_halo); (void)hipFree(d_mask);
                     uniq.swap(cut); nblk = (uint32_t)(uniq.size() - 1);
                     done = true;                                           // next round on the refined boundaries
                     continue;
@@ -199,7 +189,7 @@ int build_plan(bvg_graph* g, uint32_t block_bits, std::shared_ptr<Plan>& out) {
                     fprintf(stderr, "[bvg] plan: %u blocks, %llu halo nodes (%.1f %% of %lld nodes)\n", nblk, (unsigned long long)hn, 100.0 * (double)hn / (double)n, (long long)n);
                 }
             }
-            plan.d_first = d_first; plan.d_halo = d_halo; plan.d_mask = d_mask;
+            plan.d_first = std::move(d_first); plan.d_halo = std::move(d_halo); plan.d_mask = std::move(d_mask);
             plan.nblk = nblk; plan.h_first = uniq; plan.h_maxd.swap(maxd);
             plan.version = next_plan_version();
             return publish();
@@ -209,7 +199,6 @@ int build_plan(bvg_graph* g, uint32_t block_bits, std::shared_ptr<Plan>& out) {
         for (uint32_t k = 0; k < nblk; k++) if (halo[k] != 0xFFFFFFFFu || k == 0) kept.push_back(uniq[k]);
         kept.push_back((uint64_t)n);
         uniq.swap(kept); nblk = (uint32_t)(uniq.size() - 1);
-        (void)hipFree(d_first); (void)hipFree(d_halo); (void)hipFree(d_mask);
       }
       if (!done) break;
     }
@@ -233,74 +222,76 @@ int read_offset(const Shared* sh, int64_t x, uint64_t* out) {
 // the plain array.  A host array is staged through a 128 MiB device buffer, so the plain form never exists in HBM.
 int pack_offsets(Shared* sh, const uint64_t* src_dev, const uint64_t* src_host) {
     const int64_t n1 = sh->p.nodes + 1, G = (int64_t)1 << kOffShift;
-    DevBuf lo, hi, ovf, stagebuf;
-    if (lo.alloc((size_t)n1 * sizeof(uint32_t)) || hi.alloc((size_t)((n1 + G - 1) / G + 1) * sizeof(uint64_t)) || ovf.alloc(sizeof(unsigned))) return BVG_E_NOMEM;
-    HIPCHK(hipMemset(ovf.p, 0, sizeof(unsigned)));
-    if (src_dev) launch_pack_offsets(src_dev, 0, n1, (uint32_t*)lo.p, (uint64_t*)hi.p, (unsigned*)ovf.p, nullptr);
+    DevArray<uint32_t> lo; DevArray<uint64_t> hi, stagebuf; DevArray<unsigned> ovf;
+    if (lo.alloc((size_t)n1) || hi.alloc((size_t)((n1 + G - 1) / G + 1)) || ovf.alloc(1)) return BVG_E_NOMEM;
+    HIPCHK(hipMemset(ovf, 0, sizeof(unsigned)));
+    if (src_dev) launch_pack_offsets(src_dev, 0, n1, lo, hi, ovf, nullptr);
     else {
         const int64_t step = (int64_t)1 << 24;
-        if (stagebuf.alloc((size_t)std::min<int64_t>(step, n1) * sizeof(uint64_t))) return BVG_E_NOMEM;
+        if (stagebuf.alloc((size_t)std::min<int64_t>(step, n1))) return BVG_E_NOMEM;
         for (int64_t first = 0; first < n1; first += step) {
             const int64_t cnt = std::min<int64_t>(step, n1 - first);
-            HIPCHK(hipMemcpy(stagebuf.p, src_host + first, (size_t)cnt * sizeof(uint64_t), hipMemcpyHostToDevice));
-            launch_pack_offsets((const uint64_t*)stagebuf.p, first, cnt, (uint32_t*)lo.p, (uint64_t*)hi.p, (unsigned*)ovf.p, nullptr);
+            HIPCHK(hipMemcpy(stagebuf, src_host + first, (size_t)cnt * sizeof(uint64_t), hipMemcpyHostToDevice));
+            launch_pack_offsets(stagebuf, first, cnt, lo, hi, ovf, nullptr);
             HIPCHK(hipStreamSynchronize(nullptr));
         }
     }
     unsigned o = 0;
-    HIPCHK(hipMemcpy(&o, ovf.p, sizeof o, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&o, ovf, sizeof o, hipMemcpyDeviceToHost));
     if (o) return 1;
-    sh->d_off_lo = (uint32_t*)lo.release(); sh->d_off_hi = (uint64_t*)hi.release();
+    sh->d_off_lo = std::move(lo); sh->d_off_hi = std::move(hi);
     sh->offs = Offsets{sh->d_off_lo, sh->d_off_hi, nullptr};
     return 0;
 }
 
 
 int open_common(const bvg_params* p, const uint8_t* h_graph, const void* d_graph_in, uint64_t nbytes, const uint64_t* h_offsets,
-                const void* d_offsets_in, int device, bvg_graph** out, const PackedOffsets* packed) {
+                const void* d_offsets_in, int device, bvg_graph** out, PackedOffsets* packed) {
     if (!p || !out) return BVG_E_ARG;
     int r = check_params(*p); if (r) return r;
     r = ensure_device(device); if (r) return r;
-    Shared* sh = new Shared();
+    struct Release { void operator()(Shared* s) const { release_shared(s); } };
+    std::unique_ptr<Shared, Release> owner(new Shared());   // released on every return but the last
+    Shared* sh = owner.get();
     sh->device = device; sh->p = *p; sh->nbytes = nbytes;
     // 32-bit successor arithmetic holds every node id below 2^32 - 1 (0xFFFFFFFF is the lists' sentinel); the reference's own line between
     // the int and the long library is 2^31 because Java ints are signed -- nothing here is
     sh->wide = p->nodes > (int64_t)0xFFFFFF00ll || (knob("BVG_WIDE_FROM_2_31") != nullptr && p->nodes > (int64_t)0x7FFFFFFF);
     const int64_t n = p->nodes;
-    if (d_graph_in) { sh->d_graph = (uint8_t*)d_graph_in; sh->own_graph = false; sh->padded = ((nbytes + 15) & ~15ull) + 16; }
+    if (d_graph_in) { sh->d_graph = (uint8_t*)d_graph_in; sh->padded = ((nbytes + 15) & ~15ull) + 16; }
     else {
         uint64_t padded = ((nbytes + 15) & ~15ull) + kPad;
         sh->padded = padded;
-        HIPCHK(hipMalloc(&sh->d_graph, padded));
-        sh->own_graph = true;
+        r = sh->own_graph.alloc(padded); if (r) return r;
+        sh->d_graph = sh->own_graph;
         HIPCHK(hipMemset(sh->d_graph, 0, padded));
         if (nbytes) HIPCHK(hipMemcpy(sh->d_graph, h_graph, nbytes, hipMemcpyHostToDevice));
     }
     // The index is kept packed (bvg_kernels.h: Offsets).  A caller's device array is packed into memory of our own and not referenced
     // afterwards; BVG_WIDE_OFFSETS=1 or a distance that does not fit 32 bits keeps the plain 64-bit form.
     const bool keep_wide = knob("BVG_WIDE_OFFSETS") != nullptr;
-    if (packed) { sh->d_off_lo = packed->lo; sh->d_off_hi = packed->hi; sh->offs = Offsets{packed->lo, packed->hi, nullptr}; }
+    if (packed) { sh->d_off_lo = std::move(packed->lo); sh->d_off_hi = std::move(packed->hi); sh->offs = Offsets{sh->d_off_lo, sh->d_off_hi, nullptr}; }
     else if (d_offsets_in) {
         int pk = keep_wide ? 1 : pack_offsets(sh, (const uint64_t*)d_offsets_in, nullptr);
-        if (pk < 0) { release_shared(sh); return pk; }
-        if (pk) { sh->d_off_wide = (uint64_t*)d_offsets_in; sh->own_wide = false; sh->offs = Offsets{nullptr, nullptr, sh->d_off_wide}; }
+        if (pk < 0) return pk;
+        if (pk) sh->offs = Offsets{nullptr, nullptr, (const uint64_t*)d_offsets_in};
     } else if (h_offsets) {
         int pk = keep_wide ? 1 : pack_offsets(sh, nullptr, h_offsets);
-        if (pk < 0) { release_shared(sh); return pk; }
+        if (pk < 0) return pk;
         if (pk) {
-            HIPCHK(hipMalloc(&sh->d_off_wide, ((size_t)n + 1) * sizeof(uint64_t)));
-            sh->own_wide = true; sh->offs = Offsets{nullptr, nullptr, sh->d_off_wide};
-            HIPCHK(hipMemcpy(sh->d_off_wide, h_offsets, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+            r = sh->own_wide.alloc((size_t)n + 1); if (r) return r;
+            sh->offs = Offsets{nullptr, nullptr, sh->own_wide};
+            HIPCHK(hipMemcpy(sh->own_wide, h_offsets, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
         }
     } else {
-        uint64_t* d_wide = nullptr;
-        HIPCHK(hipMalloc(&d_wide, ((size_t)n + 1) * sizeof(uint64_t)));
-        sh->d_off_wide = d_wide; sh->own_wide = true; sh->offs = Offsets{nullptr, nullptr, d_wide};
+        r = sh->own_wide.alloc((size_t)n + 1); if (r) return r;
+        uint64_t* const d_wide = sh->own_wide;
+        sh->offs = Offsets{nullptr, nullptr, d_wide};
         {
             // no .offsets (loadSequential / loadOffline, BVG:1345-1464; BVGraph -O, BVG:2595-2609): derive the index from
             // the stream itself with one sequential pass on the device
-            unsigned* d_err = nullptr;
-            HIPCHK(hipMalloc(&d_err, sizeof(unsigned)));
+            DevArray<unsigned> d_err;
+            r = d_err.alloc(1); if (r) return r;
             HIPCHK(hipMemset(d_err, 0, sizeof(unsigned)));
             // Default: the chunk-parallel walk of bvg_derive.hip (round 3: one code per lane and step, only changed chunks re-walked).
             // Fall-back -- windows > 127, any oddity in the stream, BVG_DERIVE_SEQ=1 -- is the one-wavefront sequential walk, whose error
@@ -309,26 +300,24 @@ int open_common(const bvg_params* p, const uint8_t* h_graph, const void* d_graph
             int pr = knob("BVG_DERIVE_SEQ") ? -1 : derive_offsets_parallel(sh->d_graph, nbytes, n, p->window_size, p->min_interval_length, codings_of(*p), d_wide, d_err, nullptr, &rounds);
             if (pr == 0) {
                 unsigned e0 = 0;
-                if (hipMemcpy(&e0, d_err, sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipFree(d_err); release_shared(sh); return BVG_E_HIP; }
+                if (hipMemcpy(&e0, d_err, sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) return BVG_E_HIP;
                 if (e0) { pr = -4; (void)hipMemset(d_err, 0, sizeof(unsigned)); }
             }
             if (dbg_on()) fprintf(stderr, "[bvg] derive offsets: parallel walk %s (%d rounds)\n", pr == 0 ? "ok" : "not used / failed", rounds);
             if (pr != 0) launch_derive_offsets(sh->d_graph, sh->padded, nbytes, n, p->window_size, p->min_interval_length, codings_of(*p), d_wide, d_err, nullptr);
             unsigned herr = 0;
-            hipError_t e = hipMemcpy(&herr, d_err, sizeof(unsigned), hipMemcpyDeviceToHost);
-            (void)hipFree(d_err);
-            if (e != hipSuccess) { release_shared(sh); return BVG_E_HIP; }
+            if (hipMemcpy(&herr, d_err, sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) return BVG_E_HIP;
             if (dbg_on()) { uint64_t last = 0; (void)hipMemcpy(&last, d_wide + n, 8, hipMemcpyDeviceToHost); fprintf(stderr, "[bvg] derive offsets: err=%u end=%llu of %llu bits\n", herr, (unsigned long long)last, (unsigned long long)nbytes * 8); }
-            if (herr) { release_shared(sh); return (herr & ERR_REF_RANGE) ? BVG_E_STATE : BVG_E_EOF; }
+            if (herr) return (herr & ERR_REF_RANGE) ? BVG_E_STATE : BVG_E_EOF;
         }
         int pk = keep_wide ? 1 : pack_offsets(sh, d_wide, nullptr);
-        if (pk < 0) { release_shared(sh); return pk; }
-        if (pk == 0) { (void)hipFree(d_wide); sh->d_off_wide = nullptr; sh->own_wide = false; }
+        if (pk < 0) return pk;
+        if (pk == 0) sh->own_wide.reset();
     }
-    r = read_offset(sh, n, &sh->total_bits); if (r) { release_shared(sh); return r; }
-    if (sh->total_bits > nbytes * 8) { release_shared(sh); return BVG_E_EOF; }
-    r = make_handle(sh, out);
-    if (r) { release_shared(sh); return r; }
+    r = read_offset(sh, n, &sh->total_bits); if (r) return r;
+    if (sh->total_bits > nbytes * 8) return BVG_E_EOF;
+    r = make_handle(sh, out); if (r) return r;
+    (void)owner.release();
     return 0;
 }
 
@@ -360,15 +349,15 @@ int cut_batches(bvg_graph* g, const uint64_t* d_cum, int64_t n, uint64_t arcs, u
     if (arcs == 0) return 0;
     if (per == 0) per = 1;
     const uint64_t nb = (arcs + per - 1) / per;
-    DevBuf first, at, before;
-    if (first.alloc((nb + 1) * 8) || at.alloc((nb + 1) * 8) || before.alloc((nb + 1) * 8)) return BVG_E_NOMEM;
-    uint64_t* const d_first = (uint64_t*)first.p; uint64_t* const d_at = (uint64_t*)at.p; uint64_t* const d_before = (uint64_t*)before.p;
+    DevArray<uint64_t> first, at, before;
+    if (first.alloc(nb + 1) || at.alloc(nb + 1) || before.alloc(nb + 1)) return BVG_E_NOMEM;
+    uint64_t* const d_first = first; uint64_t* const d_at = at; uint64_t* const d_before = before;
     launch_plan_boundaries(Offsets{nullptr, nullptr, d_cum}, n, per, nb, d_first, g->stream);
     hipLaunchKernelGGL(gather_bounds_kernel, dim3(grid((int64_t)nb + 1, 256)), dim3(256), 0, g->stream, d_cum, (const uint64_t*)d_first, nb, d_at, d_before);
     std::vector<uint64_t> hf(nb + 1), ha(nb + 1), hb(nb + 1);
-    HIPCHK(hipMemcpyAsync(hf.data(), first.p, (nb + 1) * 8, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(ha.data(), at.p, (nb + 1) * 8, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(hb.data(), before.p, (nb + 1) * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(hf.data(), d_first, (nb + 1) * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(ha.data(), d_at, (nb + 1) * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(hb.data(), d_before, (nb + 1) * 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     for (uint64_t j = 0; j < nb; j++) {
         const uint64_t b0 = hf[j], b1 = hf[j + 1];
@@ -390,15 +379,15 @@ int cut_batches(bvg_graph* g, const uint64_t* d_cum, int64_t n, uint64_t arcs, u
 // [0, nodes) cut into node ranges that way: the whole graph's outdegrees and their prefix sums are computed on the device
 int plan_batches(bvg_graph* g, uint64_t per, std::vector<Batch>& out, uint64_t* arcs_out, uint64_t* longest_out) {
     Shared* sh = g->sh; const int64_t n = sh->p.nodes;
-    DevBuf deg, cum, tmp;
-    if (deg.alloc((size_t)n * 4) || cum.alloc(((size_t)n + 1) * 8) || tmp.alloc(scan_tmp_elems(n) * 8)) return BVG_E_NOMEM;
-    outdegrees_of(g, 0, n, (int32_t*)deg.p);
-    launch_exclusive_scan((const int32_t*)deg.p, (uint64_t*)cum.p, n, (uint64_t*)tmp.p, g->stream);
+    DevArray<int32_t> deg; DevArray<uint64_t> cum, tmp;
+    if (deg.alloc((size_t)n) || cum.alloc((size_t)n + 1) || tmp.alloc(scan_tmp_elems(n))) return BVG_E_NOMEM;
+    outdegrees_of(g, 0, n, deg);
+    launch_exclusive_scan(deg, cum, n, tmp, g->stream);
     uint64_t arcs = 0;
-    HIPCHK(hipMemcpyAsync(&arcs, (uint64_t*)cum.p + n, 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(&arcs, cum + n, 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     *arcs_out = arcs;
-    return cut_batches(g, (const uint64_t*)cum.p, n, arcs, per, out, longest_out);
+    return cut_batches(g, cum, n, arcs, per, out, longest_out);
 }
 
 // ---- the sweep: the whole graph decoded in arc-bounded node ranges, each consumed at once by the caller's kernel

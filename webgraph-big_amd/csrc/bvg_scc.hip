@@ -212,7 +212,6 @@ template <typename T> __global__ void scc_buckets_kernel(const T* rep, const uin
 namespace {
 
 using bvghost::Batch;
-using bvghost::DevBuf;
 
 constexpr int kMaxReruns = 8;       // of the kernel on one resident batch of several, while it still changes something (a stated default, not measured)
 
@@ -303,12 +302,12 @@ template <typename T> int scc_t(bvg_graph* g, uint32_t flags, int64_t* comp, int
     const int64_t n = g->sh->p.nodes;
     const bool dbgt = dbg_on();
     Stopwatch sw;
-    DevBuf rep, colour, fl, ctl, dbuck;
-    if (rep.alloc((size_t)n * sizeof(T)) || colour.alloc((size_t)n * sizeof(T)) || fl.alloc(((size_t)n + 3) & ~(size_t)3) || ctl.alloc(kCtlWords * 8)) return BVG_E_NOMEM;
+    DevArray<T> rep, colour; DevArray<uint8_t> fl, dbuck; DevArray<unsigned long long> ctl;
+    if (rep.alloc((size_t)n) || colour.alloc((size_t)n) || fl.alloc(((size_t)n + 3) & ~(size_t)3) || ctl.alloc(kCtlWords)) return BVG_E_NOMEM;
     uint8_t* d_buckets = buckets;
-    if ((flags & BVG_SCC_BUCKETS) && !dev) { if (dbuck.alloc((size_t)n)) return BVG_E_NOMEM; d_buckets = (uint8_t*)dbuck.p; }
+    if ((flags & BVG_SCC_BUCKETS) && !dev) { if (dbuck.alloc((size_t)n)) return BVG_E_NOMEM; d_buckets = dbuck; }
     SccRun<T> r;
-    r.g = g; r.n = n; r.rep = (T*)rep.p; r.colour = (T*)colour.p; r.flags = (uint8_t*)fl.p; r.ctl = (unsigned long long*)ctl.p;
+    r.g = g; r.n = n; r.rep = rep; r.colour = colour; r.flags = fl; r.ctl = ctl;
     hipLaunchKernelGGL((scc_init_kernel<T>), dim3(grid(n, 256)), dim3(256), 0, g->stream, r.rep, r.colour, r.flags, n);
     index_first(g);
     uint64_t per = 0;                                                       // (of what is free once the per-node arrays are there)
@@ -317,8 +316,8 @@ template <typename T> int scc_t(bvg_graph* g, uint32_t flags, int64_t* comp, int
     r.counters[kResident] = r.sp.single() ? 1 : 0;
     uint64_t live = (uint64_t)n;
     {
-        DevBuf ws;                                                          // (this scope: gone before the numbering pass, which needs the memory)
-        if (!r.sp.batches.empty()) { if (ws.alloc(r.sp.bytes)) return BVG_E_NOMEM; r.sp.bind(ws.p); }
+        DevArray<uint8_t> ws;                                                    // (this scope: gone before the numbering pass, which needs the memory)
+        if (!r.sp.batches.empty()) { if (ws.alloc(r.sp.bytes)) return BVG_E_NOMEM; r.sp.bind(ws.get()); }
         rc = r.trim(&live); if (rc) return rc;
         // the FW-BW step
         int64_t pivot = -1; bool want_step = live != 0;
@@ -360,11 +359,11 @@ template <typename T> int scc_t(bvg_graph* g, uint32_t flags, int64_t* comp, int
         }
         HIPCHK(hipStreamSynchronize(g->stream));
     }
-    (void)hipFree(colour.release()); (void)hipFree(fl.release());            // the numbering takes 12 bytes per node of its own
+    colour.reset(); fl.reset();                                              // the numbering takes 12 bytes per node of its own
     const double t_scc = sw.lap();
     if (counters) memcpy(counters, r.counters, sizeof r.counters);
     uint64_t count = 0;
-    rc = number_components(g, rep.p, sizeof(T) == 8, (flags & BVG_SCC_SORT_BY_SIZE) ? BVG_CC_SORT_BY_SIZE : 0u, comp, sizes, sizes_cap, n_components, dev, &count);
+    rc = number_components(g, rep.get(), sizeof(T) == 8, (flags & BVG_SCC_SORT_BY_SIZE) ? BVG_CC_SORT_BY_SIZE : 0u, comp, sizes, sizes_cap, n_components, dev, &count);
     if (rc && rc != BVG_E_CAPACITY) return rc;
     if ((flags & BVG_SCC_BUCKETS) && !dev) HIPCHK(hipMemcpy(buckets, d_buckets, (size_t)n, hipMemcpyDeviceToHost));
     if (dbgt) fprintf(stderr, "[bvg] scc: %zu batches of <= %llu arcs (%llu arcs), %llu sweeps, %llu decodes, %llu trim passes (%llu nodes), fw-bw %llu nodes, %llu rounds (%llu components): "

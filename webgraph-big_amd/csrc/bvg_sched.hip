@@ -77,7 +77,7 @@ struct Decode {
     DecodeArgs a{}, af{};                   // the row kernels' arguments, the lean scan kernel's
     bool giant_ok = false, predict = false, fast_ok = false; uint32_t lean_waves = 0;
     uint32_t launches = 0, slow_blocks = 0, lean_blocks = 0; double kernel_ms = 0; bool predicted_run = false;   // (cascade outcomes of a predicted run are remembered in g->pred2)
-    std::vector<uint32_t> work; DevBuf d_work;   // the blocks the next tier runs
+    std::vector<uint32_t> work; DevArray<uint32_t> d_work;   // the blocks the next tier runs
     Decode(bvg_graph* g_, std::shared_ptr<Plan> p, int64_t f, int64_t t, bool m, const BatchPlan* b, bvg_scan_result* r)
         : g(g_), sh(g_->sh), plp(std::move(p)), pl(*plp), from(f), to(t), materialise(m), batch(b), res(r), k(read_knobs()) {
         force_slow = g->tun.force_slow || sh->p.window_size > kMaxWindow;   // wide windows: the generic global-memory kernel only
@@ -113,18 +113,17 @@ struct Decode {
         return 0;
     }
     int upload_work() {
-        if (d_work.p) (void)hipFree(d_work.release());
-        void* p = nullptr; HIPCHK(hipMalloc(&p, work.size() * sizeof(uint32_t))); d_work.p = p;
-        HIPCHK(hipMemcpy(d_work.p, work.data(), work.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (d_work.alloc(work.size())) return BVG_E_NOMEM;
+        HIPCHK(hipMemcpy(d_work, work.data(), work.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         HIPCHK(hipMemsetAsync(g->d_fail, 0, sizeof(uint32_t), g->stream));
-        a.work_list = static_cast<uint32_t*>(d_work.p);
+        a.work_list = d_work;
         return 0;
     }
     // the LDS tiers' kernel (tier 0 and, is_class, the size classes): the row kernel, or the experiment selected in its place
     void launch_lds(const DecodeArgs& aa, uint32_t nb, hipStream_t st, bool is_class = false) {
         if (x.tier0 == Experiments::kStream && !is_class) launch_stream_decode(aa, nb, wide, materialise, st);
         else if (x.tier0 == Experiments::kLegacy) launch_decode(aa, nb, wide, materialise, false, st);
-        else if (x.flow && !is_class && aa.work_list == pred().d_lists) launch_flow_scan(aa, nb, g->flow_waves, g->flow_ws, x.flow_ring, st);
+        else if (x.flow && !is_class && aa.work_list == pred().d_lists) launch_flow_scan(aa, nb, g->flow_waves, g->flow_ws.get(), x.flow_ring, st);
         else if (const int nw = is_class && x.wg_class ? x.wg_class : x.wg_nw) launch_rows_wg_decode(aa, nb, nw, st);
         else launch_rows_decode(aa, nb, wide, materialise, st);
     }
@@ -168,9 +167,9 @@ static int ensure_skip(Decode& d, bool& done) {
 static int base_args(Decode& d, const uint64_t* d_cum, int64_t* d_succ, int32_t* d_outdeg) {
     bvg_graph* g = d.g; Shared* sh = d.sh; DecodeArgs& a = d.a;
     if (d.nblocks > g->fail_cap) {                          // every block may fail over to the slow path
-        (void)hipFree(g->d_fail); g->d_fail = nullptr;
+        g->fail_cap = 0;
+        if (g->d_fail.alloc(2 * (size_t)d.nblocks + 1)) return BVG_E_NOMEM;
         g->fail_cap = d.nblocks;
-        HIPCHK(hipMalloc(&g->d_fail, (2 * (size_t)g->fail_cap + 1) * sizeof(uint32_t)));
     }
     HIPCHK(hipMemsetAsync(g->d_acc, 0, (size_t)kAccStripes * kAccStride * sizeof(unsigned long long), g->stream));
     HIPCHK(hipMemsetAsync(g->d_fail, 0, sizeof(uint32_t), g->stream));
@@ -231,11 +230,8 @@ static void select_experiments(Decode& d) {
         const size_t per = flow_scratch_bytes_per_wave(d.sh->p.window_size);
         const uint32_t per_cu = (uint32_t)std::min<size_t>(20, (160 * 1024) / (flow_lds_bytes(x.flow_ring) + 1536 + 64));
         const uint32_t waves = 256u * std::max(1u, per_cu);
-        if (g->flow_waves != waves || g->flow_ws_bytes < per * waves) {
-            if (g->flow_ws) { (void)hipFree(g->flow_ws); g->flow_ws = nullptr; g->flow_ws_bytes = 0; }
-            if (hipMalloc(&g->flow_ws, per * waves) != hipSuccess) { (void)hipGetLastError(); x.flow = false; }
-            else { g->flow_ws_bytes = per * waves; g->flow_waves = waves; }
-        }
+        if (g->flow_waves != waves) g->flow_ws.reset();                    // (another geometry: a block of its own size)
+        if (g->flow_ws.reserve(per * waves)) x.flow = false; else g->flow_waves = waves;
     }
     // The flat scan kernel (experimental/bvg_flat.hip, round 5: bit-exact, slower -- DESIGN.md) takes what the lean scan kernel takes, for scans (not materialising
     // calls) of graphs whose ids fit 32 bits, with BVG_FLAT=1; BVG_FLAT_RECS = records per super-row (64 ... 256).
@@ -381,8 +377,7 @@ static int classify_blocks(Decode& d) {
     const size_t ngiant = L[Pred::kGiant].size() + L[Pred::kGeneric].size();
     if (dbg_on() && ngiant) fprintf(stderr, "[bvg] giant blocks: %zu (%llu of them for a record longer than the window), %llu nodes in them\n", ngiant, (unsigned long long)glong, (unsigned long long)gnodes);
     pd.dirty = false; pd.mode = pmode;
-    if (pd.d_lists) { (void)hipFree(pd.d_lists); pd.d_lists = nullptr; }
-    HIPCHK(hipMalloc(&pd.d_lists, (size_t)nblocks * sizeof(uint32_t)));
+    if (pd.d_lists.alloc(nblocks)) return BVG_E_NOMEM;
     size_t off = 0;
     for (int c = 0; c < Pred::kSlots; c++) {
         pd.count[c] = (uint32_t)L[c].size();
@@ -409,17 +404,14 @@ static int giant_workspace(Decode& d, GiantWs& gw) {
     gw.slots = !d.k.gbatch;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const uint64_t per = (gw.pool_elems + gw.scr_elems) * d.esz, room = ((uint64_t)free_b + g->giant_ws_bytes) / 4;
+        const uint64_t per = (gw.pool_elems + gw.scr_elems) * d.esz, room = ((uint64_t)free_b + g->giant_ws.bytes()) / 4;
         const uint64_t fit = room / std::max<uint64_t>(per, 1);
         if (fit < gw.batch) { gw.batch = (uint32_t)std::max<uint64_t>(fit, 1); if (gw.batch < std::min<uint32_t>(kGiantResident, ngiant)) gw.slots = false; }   // too few slots for every resident workgroup: batches again
     }
     const uint64_t bytes = (uint64_t)gw.batch * (gw.pool_elems + gw.scr_elems) * d.esz;
-    if (bytes > g->giant_ws_bytes) {
-        if (g->giant_ws) { (void)hipFree(g->giant_ws); g->giant_ws = nullptr; g->giant_ws_bytes = 0; }
-        if (hipMalloc(&g->giant_ws, bytes) == hipSuccess) g->giant_ws_bytes = bytes; else gw.batch = 0;   // fall back to the cascade
-    }
+    if (g->giant_ws.reserve(bytes)) gw.batch = 0;           // fall back to the cascade
     if (gw.slots && gw.batch) {
-        if (!g->d_gslots && hipMalloc(&g->d_gslots, 8192 * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); g->d_gslots = nullptr; gw.slots = false; gw.batch = std::min<uint32_t>(gw.batch, 256u); }
+        if (!g->d_gslots && g->d_gslots.alloc(8192)) { gw.slots = false; gw.batch = std::min<uint32_t>(gw.batch, 256u); }
         if (gw.slots) HIPCHK(hipMemsetAsync(g->d_gslots, 0, 8192 * sizeof(uint32_t), g->stream));   // (ordered before the side streams by ev0 below)
     }
     return 0;
@@ -449,12 +441,12 @@ static int launch_concurrent(Decode& d, const GiantWs& gw) {
     };
     if (k.tier0_first) { row0(); lean0(); }
     if (gw.batch && pd.count[Pred::kGiant] + pd.count[Pred::kGeneric]) {   // giants first: they are the critical path
-        DecodeArgs ag = d.a; ag.gpool = g->giant_ws; ag.gpool_elems = gw.pool_elems;
+        DecodeArgs ag = d.a; ag.gpool = g->giant_ws.get(); ag.gpool_elems = gw.pool_elems;
         if (ag.skip_mode == 3) ag.skip_mode = 2;            // (the giant kernel fills its own entries, in its own format, while it validates)
-        ag.gscr = (char*)g->giant_ws + (size_t)gw.batch * gw.pool_elems * d.esz; ag.gscr_elems = gw.scr_elems; ag.lds_stage_words = 1024;
+        ag.gscr = g->giant_ws.at((size_t)gw.batch * gw.pool_elems * d.esz); ag.gscr_elems = gw.scr_elems; ag.lds_stage_words = 1024;
         for (int c = Pred::kGiant; c <= Pred::kGeneric; c++) {
             const bool slots = gw.slots && c == Pred::kGiant;   // (the generic kernel keeps one area per block of a batch)
-            ag.gslots = slots ? g->d_gslots : nullptr; ag.gnslots = slots ? gw.batch : 0u;
+            ag.gslots = slots ? g->d_gslots.get() : nullptr; ag.gnslots = slots ? gw.batch : 0u;
             const uint32_t step = slots ? std::max<uint32_t>(pd.count[c], 1u) : gw.batch;
             for (uint32_t o2 = 0; o2 < pd.count[c]; o2 += step) {
                 ag.work_list = pd.d_lists + pd.offset(c) + o2;
@@ -572,21 +564,17 @@ static int run_global_tier(Decode& d, bool giant, std::vector<uint32_t>& refused
         uint64_t per_wg = (pool_elems + scr_elems) * d.esz;
         size_t free_b = 0, total_b = 0;
         HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        uint32_t batch = (uint32_t)std::min<uint64_t>({(uint64_t)work.size(), std::max<uint64_t>(1, ((free_b + g->slow_ws_bytes) / 2) / per_wg), 1024});
-        if ((uint64_t)batch * per_wg > g->slow_ws_bytes) {
-            if (g->slow_ws) { (void)hipFree(g->slow_ws); g->slow_ws = nullptr; g->slow_ws_bytes = 0; }
-            if (hipMalloc(&g->slow_ws, (size_t)batch * per_wg) != hipSuccess) return BVG_E_NOMEM;
-            g->slow_ws_bytes = (uint64_t)batch * per_wg;
-        }
+        uint32_t batch = (uint32_t)std::min<uint64_t>({(uint64_t)work.size(), std::max<uint64_t>(1, ((free_b + g->slow_ws.bytes()) / 2) / per_wg), 1024});
+        if (g->slow_ws.reserve((size_t)batch * per_wg)) return BVG_E_NOMEM;
         int r = d.upload_work(); if (r) return r;
-        a.gpool = g->slow_ws; a.gpool_elems = pool_elems;
-        a.gscr = (char*)g->slow_ws + (size_t)batch * pool_elems * d.esz; a.gscr_elems = scr_elems;
+        a.gpool = g->slow_ws.get(); a.gpool_elems = pool_elems;
+        a.gscr = g->slow_ws.at((size_t)batch * pool_elems * d.esz); a.gscr_elems = scr_elems;
         a.lds_stage_words = 1024;
         const size_t nwork = work.size();
         r = d.timed(giant ? "tier2a (giant)" : "tier2 (generic)", nwork, [&] {
             for (size_t off = 0; off < nwork; off += batch) {
                 uint32_t nb = (uint32_t)std::min<size_t>(batch, nwork - off);
-                a.work_list = static_cast<uint32_t*>(d.d_work.p) + off;
+                a.work_list = d.d_work + off;
                 if (giant) { DecodeArgs ag2 = a; if (ag2.skip_mode == 3) ag2.skip_mode = 2; launch_giant_decode(ag2, nb, d.wide, d.materialise, g->stream); } else launch_decode(a, nb, d.wide, d.materialise, true, g->stream);
                 d.launches++;
             }

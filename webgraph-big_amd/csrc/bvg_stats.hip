@@ -213,13 +213,11 @@ template <typename V> __global__ void __launch_bounds__(256) stats_distribution_
 
 }  // namespace bvg
 
-using bvghost::DevBuf;
-
 struct bvg_stats {
     int device = 0;
     int64_t n = 0;
     bool wide = false;                                // the per-node indegrees are uint64 (else uint32)
-    DevBuf indeg;                                     // kept with BVG_STATS_KEEP_INDEGREES
+    DevArray<uint8_t> indeg;                          // (bytes: 4 or 8 per node) kept with BVG_STATS_KEEP_INDEGREES
     bool keep = false;
     bvg_stats_summary sum{};
     std::vector<uint64_t> dist[2];                    // [BVG_STATS_OUT], [BVG_STATS_IN]
@@ -237,12 +235,12 @@ struct HostExtremes { uint64_t minv = 0, maxv = 0; int64_t minn = -1, maxn = -1;
 template <typename V, bool LARGE> int extremes_of(bvg_graph* g, const V* d_val, int64_t n, HostExtremes* out) {
     const unsigned blocks = std::min<unsigned>(kExtGrid, grid(n, 256));
     const size_t words = (size_t)blocks * 4 * kExtWords;
-    DevBuf part;
-    if (part.alloc(words * 8)) return BVG_E_NOMEM;
-    hipLaunchKernelGGL((stats_extremes_kernel<V, LARGE>), dim3(blocks), dim3(256), 0, g->stream, d_val, n, (unsigned long long*)part.p);
+    DevArray<unsigned long long> part;
+    if (part.alloc(words)) return BVG_E_NOMEM;
+    hipLaunchKernelGGL((stats_extremes_kernel<V, LARGE>), dim3(blocks), dim3(256), 0, g->stream, d_val, n, part.get());
     HIPCHK(hipGetLastError());
     std::vector<unsigned long long> h(words);
-    HIPCHK(hipMemcpyAsync(h.data(), part.p, words * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(h.data(), part.get(), words * 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     HostExtremes e;
     auto better = [](bool less, uint64_t v, int64_t x, uint64_t bv, int64_t bx) {
@@ -264,13 +262,13 @@ template <typename V, bool LARGE> int extremes_of(bvg_graph* g, const V* d_val, 
 // the count of counts of d_val[0, n), whose largest value is maxv, into `out` (maxv + 1 entries)
 template <typename V> int distribution_of(bvg_graph* g, const V* d_val, int64_t n, uint64_t maxv, std::vector<uint64_t>& out) {
     const uint64_t len = maxv + 1;
-    DevBuf dist;
-    if (dist.alloc(len * 8)) return BVG_E_NOMEM;
-    HIPCHK(hipMemsetAsync(dist.p, 0, len * 8, g->stream));
-    hipLaunchKernelGGL((stats_distribution_kernel<V>), dim3(std::min<unsigned>(1024, grid(n, 4096))), dim3(256), 0, g->stream, d_val, n, (unsigned long long*)dist.p, len);
+    DevArray<unsigned long long> dist;
+    if (dist.alloc(len)) return BVG_E_NOMEM;
+    HIPCHK(hipMemsetAsync(dist.get(), 0, len * 8, g->stream));
+    hipLaunchKernelGGL((stats_distribution_kernel<V>), dim3(std::min<unsigned>(1024, grid(n, 4096))), dim3(256), 0, g->stream, d_val, n, dist.get(), len);
     HIPCHK(hipGetLastError());
     out.resize(len);
-    HIPCHK(hipMemcpyAsync(out.data(), dist.p, len * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(out.data(), dist.get(), len * 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     return 0;
 }
@@ -282,26 +280,26 @@ template <typename T> int stats_t(bvg_graph* g, bvg_stats* s) {
     Stopwatch sw;
     index_first(g);
     if (s->indeg.alloc((size_t)n * sizeof(T))) return BVG_E_NOMEM;
-    T* const d_indeg = (T*)s->indeg.p;
+    T* const d_indeg = (T*)s->indeg.get();
     HIPCHK(hipMemsetAsync(d_indeg, 0, (size_t)n * sizeof(T), g->stream));
     bvg_stats_summary& r = s->sum;
     {   // every node's outdegree (4 bytes per node, gone before the batch is sized)
-        DevBuf deg;
-        if (deg.alloc((size_t)n * 4)) return BVG_E_NOMEM;
-        outdegrees_of(g, 0, n, (int32_t*)deg.p);
+        DevArray<int32_t> deg;
+        if (deg.alloc((size_t)n)) return BVG_E_NOMEM;
+        outdegrees_of(g, 0, n, deg);
         HostExtremes e;
-        int rc = extremes_of<uint32_t, false>(g, (const uint32_t*)deg.p, n, &e); if (rc) return rc;
+        int rc = extremes_of<uint32_t, false>(g, (const uint32_t*)deg.get(), n, &e); if (rc) return rc;
         if (e.maxv > 0x7FFFFFFFull) return BVG_E_UNSUPPORTED;                // (Stats.java:120)
         r.min_outdegree = (int64_t)e.minv; r.min_outdegree_node = e.minn; r.max_outdegree = (int64_t)e.maxv; r.max_outdegree_node = e.maxn;
         r.dangling = e.zeros;
-        rc = distribution_of<uint32_t>(g, (const uint32_t*)deg.p, n, e.maxv, s->dist[BVG_STATS_OUT]); if (rc) return rc;
+        rc = distribution_of<uint32_t>(g, (const uint32_t*)deg.get(), n, e.maxv, s->dist[BVG_STATS_OUT]); if (rc) return rc;
     }
-    DevBuf accb;
-    if (accb.alloc(kAccWords * 8)) return BVG_E_NOMEM;
+    DevArray<unsigned long long> accb;
+    if (accb.alloc(kAccWords)) return BVG_E_NOMEM;
     unsigned long long h_acc[kAccWords] = {};
     if (const char* k = knob("BVG_STATS_SUM_SEED")) h_acc[kGapLo] = h_acc[kLocLo] = strtoull(k, nullptr, 0);
-    HIPCHK(hipMemcpyAsync(accb.p, h_acc, sizeof h_acc, hipMemcpyHostToDevice, g->stream));
-    unsigned long long* const d_acc = (unsigned long long*)accb.p;
+    HIPCHK(hipMemcpyAsync(accb, h_acc, sizeof h_acc, hipMemcpyHostToDevice, g->stream));
+    unsigned long long* const d_acc = accb;
     const double t_deg = sw.lap();
     uint64_t per = 0;                                                       // (of what is free once the indegrees are there)
     int rc = arc_budget(n, kMaxBatchArcs, "BVG_STATS_BATCH_ARCS", &per); if (rc) return rc;
@@ -310,9 +308,9 @@ template <typename T> int stats_t(bvg_graph* g, bvg_stats* s) {
     const double t_plan = sw.lap();
     double t_dec = 0, t_arc = 0;
     if (!sp.batches.empty()) {
-        DevBuf ws;
+        DevArray<uint8_t> ws;
         if (ws.alloc(sp.bytes)) return BVG_E_NOMEM;                         // indegrees + the largest batch: does not fit
-        sp.bind(ws.p);
+        sp.bind(ws.get());
         for (const Batch& b : sp.batches) {
             const int64_t cnt = b.hi - b.lo;
             sw.lap();
@@ -352,7 +350,7 @@ int stats_impl(bvg_graph* g, uint32_t flags, bvg_stats* s) {
     HIPCHK(hipSetDevice(sh->device));
     const int rc = s->wide ? stats_t<uint64_t>(g, s) : stats_t<uint32_t>(g, s);
     if (rc) return rc;
-    if (!s->keep) { (void)hipFree(s->indeg.release()); }
+    if (!s->keep) s->indeg.reset();
     return 0;
 }
 
@@ -369,11 +367,11 @@ int indegrees_impl(bvg_stats* s, int64_t from, int64_t to, int64_t* out, bool de
     if (!out) return BVG_E_ARG;
     HIPCHK(hipSetDevice(s->device));
     const int64_t cnt = to - from;
-    DevBuf tmp;
+    DevArray<int64_t> tmp;
     int64_t* d_out = out;
-    if (!dev) { if (tmp.alloc((size_t)cnt * 8)) return BVG_E_NOMEM; d_out = (int64_t*)tmp.p; }
-    if (s->wide) hipLaunchKernelGGL((stats_widen_kernel<uint64_t>), dim3(grid(cnt, 256)), dim3(256), 0, nullptr, (const uint64_t*)s->indeg.p + from, cnt, d_out);
-    else hipLaunchKernelGGL((stats_widen_kernel<uint32_t>), dim3(grid(cnt, 256)), dim3(256), 0, nullptr, (const uint32_t*)s->indeg.p + from, cnt, d_out);
+    if (!dev) { if (tmp.alloc((size_t)cnt)) return BVG_E_NOMEM; d_out = tmp; }
+    if (s->wide) hipLaunchKernelGGL((stats_widen_kernel<uint64_t>), dim3(grid(cnt, 256)), dim3(256), 0, nullptr, (const uint64_t*)s->indeg.get() + from, cnt, d_out);
+    else hipLaunchKernelGGL((stats_widen_kernel<uint32_t>), dim3(grid(cnt, 256)), dim3(256), 0, nullptr, (const uint32_t*)s->indeg.get() + from, cnt, d_out);
     HIPCHK(hipGetLastError());
     if (!dev) HIPCHK(hipMemcpy(out, d_out, (size_t)cnt * 8, hipMemcpyDeviceToHost));
     else HIPCHK(hipStreamSynchronize(nullptr));
@@ -397,7 +395,7 @@ int bvg_stats_compute(bvg_graph* g, uint32_t flags, bvg_stats** out) {
 
 void bvg_stats_close(bvg_stats* s) {
     if (!s) return;
-    if (s->indeg.p) (void)hipSetDevice(s->device);
+    if (s->indeg) (void)hipSetDevice(s->device);
     delete s;
 }
 

@@ -411,25 +411,22 @@ int text_status(unsigned reason) { return reason == BVG_TEXT_NOT_INCREASING || r
 struct bvg_text {
     int device = 0;
     int64_t nodes = 0; uint64_t arcs = 0;
-    uint64_t* d_off = nullptr;          // adj_off[nodes + 1]
-    int64_t* d_adj = nullptr;           // adj[arcs], inside d_adj_base
-    void* d_adj_base = nullptr;
-    ~bvg_text() { (void)hipSetDevice(device); if (d_off) (void)hipFree(d_off); if (d_adj_base) (void)hipFree(d_adj_base); }
+    DevArray<uint64_t> d_off;           // adj_off[nodes + 1]
+    int64_t* d_adj = nullptr;           // adj[arcs], inside adj_base
+    DevArray<int64_t> adj_base;
+    ~bvg_text() { (void)hipSetDevice(device); }
 };
 
 namespace bvghost {
 namespace {
 
-#define TXCHK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { (void)hipGetLastError(); return _e == hipErrorOutOfMemory ? BVG_E_NOMEM : BVG_E_HIP; } } while (0)
-#define TXALLOC(buf, bytes) do { if ((buf).alloc(bytes)) return BVG_E_NOMEM; } while (0)
-
 // fills *err from a key; the line is counted on the device (error path only)
 int refuse(const uint8_t* d_text, uint64_t key, unsigned long long* d_scratch, bvg_text_error* err) {
     const uint64_t byte = key >> 4; const unsigned reason = (unsigned)(key & 15u);
     unsigned long long breaks = 0;
-    TXCHK(hipMemset(d_scratch, 0, sizeof(unsigned long long)));
+    HIPCHK(hipMemset(d_scratch, 0, sizeof(unsigned long long)));
     if (byte) hipLaunchKernelGGL(text_count_breaks_kernel, dim3(grid((int64_t)byte, 256 * 16)), dim3(256), 0, 0, d_text, byte, d_scratch);
-    TXCHK(hipMemcpy(&breaks, d_scratch, sizeof breaks, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&breaks, d_scratch, sizeof breaks, hipMemcpyDeviceToHost));
     if (err) { err->byte = byte; err->line = (int64_t)breaks + 1; err->reason = (int32_t)reason; err->reserved = 0; }
     return text_status(reason);
 }
@@ -437,42 +434,40 @@ int refuse(const uint8_t* d_text, uint64_t key, unsigned long long* d_scratch, b
 int parse_impl(bool arcs_mode, const uint8_t* d_text, uint64_t nbytes, int64_t shift, uint32_t flags, int64_t min_nodes, int device, bvg_text** out, bvg_text_error* err) {
     const uint64_t tiles = (nbytes + kTile - 1) / kTile, tl = tiles ? tiles : 1;
     if (tiles > 0x7FFFFFFFull) return BVG_E_UNSUPPORTED;                   // 8 TiB of text
-    DevBuf scal, ev, state, ctok, cbrk, btok, bbrk, tmp, vals, tb;
-    TXALLOC(scal, 8 * sizeof(unsigned long long));
-    unsigned long long* d_s = (unsigned long long*)scal.p;                 // [0] n [1] header key [2] error key [3] max id [4] T3 index [5] located [6] line count
+    DevArray<unsigned long long> scal; DevArray<uint8_t> ev, state; DevArray<int32_t> ctok, cbrk; DevArray<uint64_t> btok, bbrk, tmp, tb; DevArray<int64_t> vals;
+    if (scal.alloc(8)) return BVG_E_NOMEM;
+    unsigned long long* d_s = scal.get();                 // [0] n [1] header key [2] error key [3] max id [4] T3 index [5] located [6] line count
     unsigned long long h_s[8] = {0, kNoError, kNoError, 0, kNoError, 0, 0, 0};
-    TXCHK(hipMemcpy(d_s, h_s, sizeof h_s, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_s, h_s, sizeof h_s, hipMemcpyHostToDevice));
     ParseArgs a{};
     a.text = d_text; a.nbytes = nbytes; a.shift = shift; a.err = d_s + 2; a.max_id = d_s + 3;
     int64_t n = 0;
     if (!arcs_mode) {
         hipLaunchKernelGGL(text_header_kernel, dim3(1), dim3(1), 0, 0, d_text, nbytes, d_s);
-        TXCHK(hipMemcpy(h_s, d_s, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h_s, d_s, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         if (h_s[1] != kNoError) return refuse(d_text, h_s[1], d_s + 6, err);
         n = (int64_t)h_s[0];
     }
     a.n = n;
-    TXALLOC(ctok, tl * sizeof(int32_t)); TXALLOC(cbrk, tl * sizeof(int32_t));
-    TXALLOC(btok, (tl + 1) * sizeof(uint64_t)); TXALLOC(bbrk, (tl + 1) * sizeof(uint64_t));
-    TXALLOC(tmp, scan_tmp_elems((int64_t)tl) * sizeof(uint64_t));
-    TXCHK(hipMemset(btok.p, 0, (tl + 1) * sizeof(uint64_t))); TXCHK(hipMemset(bbrk.p, 0, (tl + 1) * sizeof(uint64_t)));
-    a.cnt_tok = (int32_t*)ctok.p; a.cnt_brk = (int32_t*)cbrk.p; a.tok_base = (uint64_t*)btok.p; a.brk_base = (uint64_t*)bbrk.p;
+    if (ctok.alloc(tl) || cbrk.alloc(tl) || btok.alloc(tl + 1) || bbrk.alloc(tl + 1) || tmp.alloc(scan_tmp_elems((int64_t)tl))) return BVG_E_NOMEM;
+    HIPCHK(hipMemset(btok.get(), 0, (tl + 1) * sizeof(uint64_t))); HIPCHK(hipMemset(bbrk.get(), 0, (tl + 1) * sizeof(uint64_t)));
+    a.cnt_tok = ctok.get(); a.cnt_brk = cbrk.get(); a.tok_base = btok.get(); a.brk_base = bbrk.get();
     uint64_t ntok = 0, nbrk = 0;
     if (tiles) {
         if (arcs_mode) {
-            TXALLOC(ev, tiles); TXALLOC(state, tiles);
-            hipLaunchKernelGGL(text_events_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, 0, d_text, nbytes, (uint8_t*)ev.p);
-            hipLaunchKernelGGL(text_state_kernel, dim3(1), dim3(kThreads), 0, 0, (const uint8_t*)ev.p, tiles, (uint8_t*)state.p);
-            a.state_in = (const uint8_t*)state.p;
+            if (ev.alloc(tiles) || state.alloc(tiles)) return BVG_E_NOMEM;
+            hipLaunchKernelGGL(text_events_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, 0, d_text, nbytes, ev.get());
+            hipLaunchKernelGGL(text_state_kernel, dim3(1), dim3(kThreads), 0, 0, ev.get(), tiles, state.get());
+            a.state_in = state.get();
             hipLaunchKernelGGL((text_pass_kernel<true, false>), dim3((unsigned)tiles), dim3(kThreads), 0, 0, a);
         } else hipLaunchKernelGGL((text_pass_kernel<false, false>), dim3((unsigned)tiles), dim3(kThreads), 0, 0, a);
-        launch_exclusive_scan(a.cnt_tok, (uint64_t*)btok.p, (int64_t)tiles, (uint64_t*)tmp.p, nullptr);
-        launch_exclusive_scan(a.cnt_brk, (uint64_t*)bbrk.p, (int64_t)tiles, (uint64_t*)tmp.p, nullptr);
-        TXCHK(hipMemcpy(&ntok, (uint64_t*)btok.p + tiles, sizeof ntok, hipMemcpyDeviceToHost));
-        TXCHK(hipMemcpy(&nbrk, (uint64_t*)bbrk.p + tiles, sizeof nbrk, hipMemcpyDeviceToHost));
+        launch_exclusive_scan(a.cnt_tok, btok.get(), (int64_t)tiles, tmp.get(), nullptr);
+        launch_exclusive_scan(a.cnt_brk, bbrk.get(), (int64_t)tiles, tmp.get(), nullptr);
+        HIPCHK(hipMemcpy(&ntok, btok.get() + tiles, sizeof ntok, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&nbrk, bbrk.get() + tiles, sizeof nbrk, hipMemcpyDeviceToHost));
     }
-    TXALLOC(vals, (ntok + 1) * sizeof(int64_t)); TXALLOC(tb, (nbrk + 1) * sizeof(uint64_t));
-    a.vals = (int64_t*)vals.p; a.tb = (uint64_t*)tb.p;
+    if (vals.alloc(ntok + 1) || tb.alloc(nbrk + 1)) return BVG_E_NOMEM;
+    a.vals = vals.get(); a.tb = tb.get();
     if (tiles) {
         if (arcs_mode) hipLaunchKernelGGL((text_pass_kernel<true, true>), dim3((unsigned)tiles), dim3(kThreads), 0, 0, a);
         else hipLaunchKernelGGL((text_pass_kernel<false, true>), dim3((unsigned)tiles), dim3(kThreads), 0, 0, a);
@@ -483,11 +478,11 @@ int parse_impl(bool arcs_mode, const uint8_t* d_text, uint64_t nbytes, int64_t s
     uint64_t look_tok = ntok, look_brk = nbrk;
     if (!arcs_mode && complete) {
         look_brk = n ? (uint64_t)n + 1 : 0; look_tok = 1;
-        if (n) TXCHK(hipMemcpy(&look_tok, (uint64_t*)tb.p + n, sizeof look_tok, hipMemcpyDeviceToHost));
+        if (n) HIPCHK(hipMemcpy(&look_tok, tb.get() + n, sizeof look_tok, hipMemcpyDeviceToHost));
     }
-    if (arcs_mode) hipLaunchKernelGGL(text_fields_kernel, dim3(grid((int64_t)nbrk + 1, 256)), dim3(256), 0, 0, (const uint64_t*)tb.p, nbrk, ntok, d_s + 4);
-    else if (look_tok > 2) hipLaunchKernelGGL(text_increasing_kernel, dim3(grid((int64_t)look_tok, 256)), dim3(256), 0, 0, (const int64_t*)vals.p, look_tok, (const uint64_t*)tb.p, look_brk, d_s + 4);
-    TXCHK(hipMemcpy(h_s, d_s, sizeof h_s, hipMemcpyDeviceToHost));
+    if (arcs_mode) hipLaunchKernelGGL(text_fields_kernel, dim3(grid((int64_t)nbrk + 1, 256)), dim3(256), 0, 0, tb.get(), nbrk, ntok, d_s + 4);
+    else if (look_tok > 2) hipLaunchKernelGGL(text_increasing_kernel, dim3(grid((int64_t)look_tok, 256)), dim3(256), 0, 0, vals.get(), look_tok, tb.get(), look_brk, d_s + 4);
+    HIPCHK(hipMemcpy(h_s, d_s, sizeof h_s, hipMemcpyDeviceToHost));
     uint64_t key = h_s[2];
     if (h_s[4] != kNoError) {
         // the smallest offending token (ASCIIGraph), line (arc lists) -> its byte offset
@@ -495,15 +490,15 @@ int parse_impl(bool arcs_mode, const uint8_t* d_text, uint64_t nbytes, int64_t s
         if (arcs_mode) {
             reason = BVG_TEXT_ARC_FIELDS;
             uint64_t tbl[2] = {0, ntok};                                    // tb[l - 1], tb[l]
-            if (index) TXCHK(hipMemcpy(&tbl[0], (uint64_t*)tb.p + index - 1, sizeof(uint64_t), hipMemcpyDeviceToHost));
-            if (index < nbrk) TXCHK(hipMemcpy(&tbl[1], (uint64_t*)tb.p + index, sizeof(uint64_t), hipMemcpyDeviceToHost));
+            if (index) HIPCHK(hipMemcpy(&tbl[0], tb.get() + index - 1, sizeof(uint64_t), hipMemcpyDeviceToHost));
+            if (index < nbrk) HIPCHK(hipMemcpy(&tbl[1], tb.get() + index, sizeof(uint64_t), hipMemcpyDeviceToHost));
             if (tbl[1] - tbl[0] == 1) { which = 1; locate = index < nbrk; }  // one number: at the break that ends the line (at the end of the text without one)
             else index = tbl[0] + 2;                                        // three or more: at the third
         }
         if (locate) {
             if (arcs_mode) hipLaunchKernelGGL((text_locate_kernel<true>), dim3(1), dim3(1), 0, 0, d_text, nbytes, a.state_in, a.tok_base, a.brk_base, tiles, which, index, d_s + 5);
             else hipLaunchKernelGGL((text_locate_kernel<false>), dim3(1), dim3(1), 0, 0, d_text, nbytes, a.state_in, a.tok_base, a.brk_base, tiles, which, index, d_s + 5);
-            TXCHK(hipMemcpy(&at, d_s + 5, sizeof at, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(&at, d_s + 5, sizeof at, hipMemcpyDeviceToHost));
         }
         const uint64_t k2 = at << 4 | reason;
         if (k2 < key) key = k2;
@@ -516,11 +511,11 @@ int parse_impl(bool arcs_mode, const uint8_t* d_text, uint64_t nbytes, int64_t s
     if (!arcs_mode) {
         if (n > kMaxNodes) return BVG_E_NOMEM;
         t->nodes = n; t->arcs = look_tok - 1;
-        TXCHK(hipMalloc(&t->d_off, ((size_t)n + 1) * sizeof(uint64_t)));
-        if (n == 0) TXCHK(hipMemset(t->d_off, 0, sizeof(uint64_t)));
-        else hipLaunchKernelGGL(text_adj_off_kernel, dim3(grid(n + 1, 256)), dim3(256), 0, 0, (const uint64_t*)tb.p, n, t->d_off);
-        TXCHK(hipDeviceSynchronize());
-        t->d_adj_base = vals.release(); t->d_adj = (int64_t*)t->d_adj_base + 1;      // behind the header's token
+        if (t->d_off.alloc((size_t)n + 1)) return BVG_E_NOMEM;
+        if (n == 0) HIPCHK(hipMemset(t->d_off, 0, sizeof(uint64_t)));
+        else hipLaunchKernelGGL(text_adj_off_kernel, dim3(grid(n + 1, 256)), dim3(256), 0, 0, tb.get(), n, t->d_off.get());
+        HIPCHK(hipDeviceSynchronize());
+        t->adj_base = std::move(vals); t->d_adj = t->adj_base + 1;                  // behind the header's token
         *out = t.release();
         return 0;
     }
@@ -534,36 +529,36 @@ int parse_impl(bool arcs_mode, const uint8_t* d_text, uint64_t nbytes, int64_t s
     if (min_nodes > nodes) nodes = min_nodes;
     if (nodes > kMaxNodes) return BVG_E_NOMEM;
     t->nodes = nodes;
-    TXCHK(hipMalloc(&t->d_off, ((size_t)nodes + 1) * sizeof(uint64_t)));
+    if (t->d_off.alloc((size_t)nodes + 1)) return BVG_E_NOMEM;
     if (np == 0) {
-        TXCHK(hipMemset(t->d_off, 0, ((size_t)nodes + 1) * sizeof(uint64_t)));
-        TXCHK(hipMalloc(&t->d_adj_base, sizeof(int64_t)));
-        t->d_adj = (int64_t*)t->d_adj_base; t->arcs = 0;
+        HIPCHK(hipMemset(t->d_off, 0, ((size_t)nodes + 1) * sizeof(uint64_t)));
+        if (t->adj_base.alloc(1)) return BVG_E_NOMEM;
+        t->d_adj = t->adj_base; t->arcs = 0;
         *out = t.release();
         return 0;
     }
     if (np > 0x7FFFFFFFull) return BVG_E_UNSUPPORTED;                      // the prefix sum below takes fewer than 2^31 elements
-    DevBuf s0, d0, s1, d1, stmp, keep, pos, ptmp;
-    TXALLOC(s0, np * 8); TXALLOC(d0, np * 8); TXALLOC(s1, np * 8); TXALLOC(d1, np * 8);
+    DevArray<uint64_t> s0, d0, s1, d1, pos, ptmp; DevArray<uint8_t> stmp; DevArray<int32_t> keep;
+    if (s0.alloc(np) || d0.alloc(np) || s1.alloc(np) || d1.alloc(np)) return BVG_E_NOMEM;
     const uint64_t drop = (uint64_t)nodes;                                 // no id reaches it
-    hipLaunchKernelGGL(text_pairs_kernel, dim3(grid((int64_t)np0, 256)), dim3(256), 0, 0, (const int64_t*)vals.p, np0, sym, nol, drop, (uint64_t*)s0.p, (uint64_t*)d0.p);
+    hipLaunchKernelGGL(text_pairs_kernel, dim3(grid((int64_t)np0, 256)), dim3(256), 0, 0, vals.get(), np0, sym, nol, drop, s0.get(), d0.get());
     const unsigned bits = bits_of(drop);
     size_t sb = 0;
-    TXCHK(rocprim::radix_sort_pairs(nullptr, sb, (const uint64_t*)d0.p, (uint64_t*)d1.p, (const uint64_t*)s0.p, (uint64_t*)s1.p, (size_t)np, 0u, bits, (hipStream_t)0));
-    TXALLOC(stmp, sb);
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, sb, (const uint64_t*)d0.get(), d1.get(), (const uint64_t*)s0.get(), s1.get(), (size_t)np, 0u, bits, (hipStream_t)0));
+    if (stmp.alloc(sb)) return BVG_E_NOMEM;
     // stable LSD: by target, then by source
-    TXCHK(rocprim::radix_sort_pairs(stmp.p, sb, (const uint64_t*)d0.p, (uint64_t*)d1.p, (const uint64_t*)s0.p, (uint64_t*)s1.p, (size_t)np, 0u, bits, (hipStream_t)0));
-    TXCHK(rocprim::radix_sort_pairs(stmp.p, sb, (const uint64_t*)s1.p, (uint64_t*)s0.p, (const uint64_t*)d1.p, (uint64_t*)d0.p, (size_t)np, 0u, bits, (hipStream_t)0));
-    TXALLOC(keep, np * sizeof(int32_t)); TXALLOC(pos, (np + 1) * sizeof(uint64_t)); TXALLOC(ptmp, scan_tmp_elems((int64_t)np) * sizeof(uint64_t));
-    hipLaunchKernelGGL(text_unique_kernel, dim3(grid((int64_t)np, 256)), dim3(256), 0, 0, (const uint64_t*)s0.p, (const uint64_t*)d0.p, np, drop, (int32_t*)keep.p);
-    launch_exclusive_scan((const int32_t*)keep.p, (uint64_t*)pos.p, (int64_t)np, (uint64_t*)ptmp.p, nullptr);
+    HIPCHK(rocprim::radix_sort_pairs(stmp.get(), sb, (const uint64_t*)d0.get(), d1.get(), (const uint64_t*)s0.get(), s1.get(), (size_t)np, 0u, bits, (hipStream_t)0));
+    HIPCHK(rocprim::radix_sort_pairs(stmp.get(), sb, (const uint64_t*)s1.get(), s0.get(), (const uint64_t*)d1.get(), d0.get(), (size_t)np, 0u, bits, (hipStream_t)0));
+    if (keep.alloc(np) || pos.alloc(np + 1) || ptmp.alloc(scan_tmp_elems((int64_t)np))) return BVG_E_NOMEM;
+    hipLaunchKernelGGL(text_unique_kernel, dim3(grid((int64_t)np, 256)), dim3(256), 0, 0, s0.get(), d0.get(), np, drop, keep.get());
+    launch_exclusive_scan(keep.get(), pos.get(), (int64_t)np, ptmp.get(), nullptr);
     uint64_t kept = 0;
-    TXCHK(hipMemcpy(&kept, (uint64_t*)pos.p + np, sizeof kept, hipMemcpyDeviceToHost));
-    TXCHK(hipMalloc(&t->d_adj_base, (kept ? kept : 1) * sizeof(int64_t)));
-    t->d_adj = (int64_t*)t->d_adj_base; t->arcs = kept;
-    hipLaunchKernelGGL(text_compact_kernel, dim3(grid((int64_t)np, 256)), dim3(256), 0, 0, (const uint64_t*)d0.p, (const int32_t*)keep.p, (const uint64_t*)pos.p, np, t->d_adj);
-    hipLaunchKernelGGL(text_arc_off_kernel, dim3(grid(nodes + 1, 256)), dim3(256), 0, 0, (const uint64_t*)s0.p, (const uint64_t*)pos.p, np, nodes, t->d_off);
-    TXCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(&kept, pos.get() + np, sizeof kept, hipMemcpyDeviceToHost));
+    if (t->adj_base.alloc(kept)) return BVG_E_NOMEM;
+    t->d_adj = t->adj_base; t->arcs = kept;
+    hipLaunchKernelGGL(text_compact_kernel, dim3(grid((int64_t)np, 256)), dim3(256), 0, 0, d0.get(), keep.get(), pos.get(), np, t->d_adj);
+    hipLaunchKernelGGL(text_arc_off_kernel, dim3(grid(nodes + 1, 256)), dim3(256), 0, 0, s0.get(), pos.get(), np, nodes, t->d_off.get());
+    HIPCHK(hipDeviceSynchronize());
     *out = t.release();
     return 0;
 }
@@ -574,12 +569,12 @@ int parse_entry(bool arcs_mode, const void* text, uint64_t nbytes, int64_t shift
     if (err) { err->byte = 0; err->line = 0; err->reason = 0; err->reserved = 0; }
     return guarded([&]() -> int {
         int r = ensure_device(device); if (r) return r;
-        DevBuf up;
+        DevArray<uint8_t> up;
         const uint8_t* d_text = (const uint8_t*)text;
         if (!dev) {
-            TXALLOC(up, nbytes);
-            if (nbytes) TXCHK(hipMemcpy(up.p, text, nbytes, hipMemcpyHostToDevice));
-            d_text = (const uint8_t*)up.p;
+            if (up.alloc(nbytes)) return BVG_E_NOMEM;
+            if (nbytes) HIPCHK(hipMemcpy(up.get(), text, nbytes, hipMemcpyHostToDevice));
+            d_text = up.get();
         }
         r = parse_impl(arcs_mode, d_text, nbytes, shift, flags, min_nodes, device, out, err);
         if (hipDeviceSynchronize() != hipSuccess && !r) r = BVG_E_HIP;
@@ -594,23 +589,22 @@ int format_dev(int kind, int64_t first_node, int64_t nodes, const uint64_t* d_of
     *nbytes = 0;
     if (a.items == 0) return 0;
     if (a.items > 0x7FFFFFFFull) return BVG_E_UNSUPPORTED;                 // one call formats fewer than 2^31 items: the writers go range by range
-    DevBuf len, pos, tmp, bad, text;
-    TXALLOC(len, a.items * sizeof(int32_t)); TXALLOC(pos, (a.items + 1) * sizeof(uint64_t)); TXALLOC(tmp, scan_tmp_elems((int64_t)a.items) * sizeof(uint64_t));
-    TXALLOC(bad, sizeof(unsigned));
-    TXCHK(hipMemset(bad.p, 0, sizeof(unsigned)));
-    hipLaunchKernelGGL(format_len_kernel, dim3(grid((int64_t)a.items, 256)), dim3(256), 0, 0, a, (int32_t*)len.p, (unsigned*)bad.p);
-    launch_exclusive_scan((const int32_t*)len.p, (uint64_t*)pos.p, (int64_t)a.items, (uint64_t*)tmp.p, nullptr);
+    DevArray<int32_t> len; DevArray<uint64_t> pos, tmp; DevArray<unsigned> bad; DevArray<uint8_t> text;
+    if (len.alloc(a.items) || pos.alloc(a.items + 1) || tmp.alloc(scan_tmp_elems((int64_t)a.items)) || bad.alloc(1)) return BVG_E_NOMEM;
+    HIPCHK(hipMemset(bad.get(), 0, sizeof(unsigned)));
+    hipLaunchKernelGGL(format_len_kernel, dim3(grid((int64_t)a.items, 256)), dim3(256), 0, 0, a, len.get(), bad.get());
+    launch_exclusive_scan(len.get(), pos.get(), (int64_t)a.items, tmp.get(), nullptr);
     uint64_t total = 0; unsigned hb = 0;
-    TXCHK(hipMemcpy(&total, (uint64_t*)pos.p + a.items, sizeof total, hipMemcpyDeviceToHost));
-    TXCHK(hipMemcpy(&hb, bad.p, sizeof hb, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&total, pos.get() + a.items, sizeof total, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&hb, bad.get(), sizeof hb, hipMemcpyDeviceToHost));
     if (hb) return BVG_E_ARG;                                              // a negative successor, or an id the shift takes out of [0, 2^63 - 1]
     *nbytes = total;
     if (!out || cap < total) return BVG_E_CAPACITY;
     uint8_t* d_out = (uint8_t*)out;
-    if (!dev) { TXALLOC(text, total); d_out = (uint8_t*)text.p; }
-    hipLaunchKernelGGL(format_write_kernel, dim3((unsigned)((a.items + kItems - 1) / kItems)), dim3(256), 0, 0, a, (const uint64_t*)pos.p, d_out);
-    if (!dev) TXCHK(hipMemcpy(out, d_out, total, hipMemcpyDeviceToHost));
-    else TXCHK(hipDeviceSynchronize());
+    if (!dev) { if (text.alloc(total)) return BVG_E_NOMEM; d_out = text.get(); }
+    hipLaunchKernelGGL(format_write_kernel, dim3((unsigned)((a.items + kItems - 1) / kItems)), dim3(256), 0, 0, a, pos.get(), d_out);
+    if (!dev) HIPCHK(hipMemcpy(out, d_out, total, hipMemcpyDeviceToHost));
+    else HIPCHK(hipDeviceSynchronize());
     return 0;
 }
 
@@ -623,18 +617,18 @@ int format_graph(int kind, bvg_graph* g, int64_t from, int64_t to, int64_t shift
         if (from == to) return 0;
         HIPCHK(hipSetDevice(g->sh->device));
         const int64_t cnt = to - from;
-        DevBuf deg, cum, tmp, succ;
-        TXALLOC(deg, (size_t)cnt * sizeof(int32_t)); TXALLOC(cum, ((size_t)cnt + 1) * sizeof(uint64_t)); TXALLOC(tmp, scan_tmp_elems(cnt) * sizeof(uint64_t));
+        DevArray<int32_t> deg; DevArray<uint64_t> cum, tmp; DevArray<int64_t> succ;
+        if (deg.alloc((size_t)cnt) || cum.alloc((size_t)cnt + 1) || tmp.alloc(scan_tmp_elems(cnt))) return BVG_E_NOMEM;
         const Shared* sh = g->sh;
-        launch_outdegrees(sh->d_graph, sh->nbytes, sh->offs, from, to, sh->p.outdegree_coding, (int32_t*)deg.p, nullptr, g->stream);
-        launch_exclusive_scan((const int32_t*)deg.p, (uint64_t*)cum.p, cnt, (uint64_t*)tmp.p, g->stream);
+        launch_outdegrees(sh->d_graph, sh->nbytes, sh->offs, from, to, sh->p.outdegree_coding, deg.get(), nullptr, g->stream);
+        launch_exclusive_scan(deg.get(), cum.get(), cnt, tmp.get(), g->stream);
         uint64_t m = 0;
-        HIPCHK(hipMemcpyAsync(&m, (uint64_t*)cum.p + cnt, sizeof m, hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipMemcpyAsync(&m, cum.get() + cnt, sizeof m, hipMemcpyDeviceToHost, g->stream));
         HIPCHK(hipStreamSynchronize(g->stream));
-        TXALLOC(succ, m * sizeof(int64_t));
-        if (m) { uint64_t got = 0; const int rc = bvg_decode_range_dev(g, from, to, nullptr, succ.p, m, &got); if (rc) return rc; }   // straight into the formatter's input
+        if (succ.alloc(m)) return BVG_E_NOMEM;
+        if (m) { uint64_t got = 0; const int rc = bvg_decode_range_dev(g, from, to, nullptr, succ.get(), m, &got); if (rc) return rc; }   // straight into the formatter's input
         HIPCHK(hipStreamSynchronize(g->stream));
-        return format_dev(kind, from + (int64_t)g->node_base, cnt, (const uint64_t*)cum.p, (const int64_t*)succ.p, m, shift, out, cap, nbytes, dev);
+        return format_dev(kind, from + (int64_t)g->node_base, cnt, cum.get(), succ.get(), m, shift, out, cap, nbytes, dev);
     });
 }
 
@@ -682,15 +676,15 @@ int bvg_text_store(bvg_text* t, const bvg_params* p, int64_t chunk_nodes, uint8_
         bvg_params q = *p; q.nodes = t->nodes;
         int r = check_params(q); if (r) return r;
         HIPCHK(hipSetDevice(t->device));
-        uint8_t* d_graph = nullptr; uint64_t* d_offsets = nullptr; uint64_t nbytes = 0;
-        r = encode_store_dev(q, t->d_off, t->d_adj, t->nodes, chunk_nodes, nullptr, &d_graph, &nbytes, &d_offsets);
+        uint8_t* pg = nullptr; uint64_t* po = nullptr; uint64_t nbytes = 0;
+        r = encode_store_dev(q, t->d_off, t->d_adj, t->nodes, chunk_nodes, nullptr, &pg, &nbytes, &po);
         if (r) return r;
-        DevBuf og, oo; og.p = d_graph; oo.p = d_offsets;
-        uint8_t* hg = (uint8_t*)calloc((size_t)nbytes + 16, 1); uint64_t* ho = (uint64_t*)malloc(((size_t)t->nodes + 1) * sizeof(uint64_t));
-        if (!hg || !ho) { free(hg); free(ho); return BVG_E_NOMEM; }
-        if ((nbytes && hipMemcpy(hg, d_graph, (size_t)nbytes, hipMemcpyDeviceToHost) != hipSuccess) ||
-            hipMemcpy(ho, d_offsets, ((size_t)t->nodes + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) { free(hg); free(ho); return BVG_E_HIP; }
-        *graph = hg; *graph_bytes = nbytes; *offsets = ho;
+        DevArray<uint8_t> d_graph; DevArray<uint64_t> d_offsets; d_graph.adopt(pg, (size_t)nbytes); d_offsets.adopt(po, (size_t)t->nodes + 1);
+        HostArray<uint8_t> hg((uint8_t*)calloc((size_t)nbytes + 16, 1)); HostArray<uint64_t> ho((uint64_t*)malloc(((size_t)t->nodes + 1) * sizeof(uint64_t)));
+        if (!hg || !ho) return BVG_E_NOMEM;
+        if ((nbytes && hipMemcpy(hg.get(), d_graph, (size_t)nbytes, hipMemcpyDeviceToHost) != hipSuccess) ||
+            hipMemcpy(ho.get(), d_offsets, ((size_t)t->nodes + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return BVG_E_HIP;
+        *graph = hg.release(); *graph_bytes = nbytes; *offsets = ho.release();
         return 0;
     });
 }
@@ -711,11 +705,11 @@ int bvg_text_format_csr(int kind, int64_t first_node, int64_t nodes, const uint6
         int device = 0;
         if (hipGetDevice(&device) != hipSuccess) { (void)hipGetLastError(); return BVG_E_HIP; }   // the calling thread's current device
         int r = ensure_device(device); if (r) return r;
-        DevBuf off, a;
-        TXALLOC(off, ((size_t)nodes + 1) * sizeof(uint64_t)); TXALLOC(a, m * sizeof(int64_t));
-        TXCHK(hipMemcpy(off.p, adj_off, ((size_t)nodes + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-        if (m) TXCHK(hipMemcpy(a.p, adj + adj_off[0], (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice));
-        return format_dev(kind, first_node, nodes, (const uint64_t*)off.p, (const int64_t*)a.p, m, kind == BVG_TEXT_ARCS ? shift : 0, out, cap, nbytes, false);
+        DevArray<uint64_t> off; DevArray<int64_t> a;
+        if (off.alloc((size_t)nodes + 1) || a.alloc(m)) return BVG_E_NOMEM;
+        HIPCHK(hipMemcpy(off.get(), adj_off, ((size_t)nodes + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+        if (m) HIPCHK(hipMemcpy(a.get(), adj + adj_off[0], (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice));
+        return format_dev(kind, first_node, nodes, off.get(), a.get(), m, kind == BVG_TEXT_ARCS ? shift : 0, out, cap, nbytes, false);
     });
 }
 
