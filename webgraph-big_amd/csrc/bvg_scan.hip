@@ -23,7 +23,7 @@
 //     are handled without branches in the position loop) -- except a stored list without reference, which is its residuals and its
 //     intervals: the residuals are decoded straight into their places (nothing parked, no level, no position task), each one shifted by
 //     the intervals below it, which a decoding task learns as its values pass their left ends; whoever passes an interval records where
-//     it starts, and the extras pass of level 0 fills the intervals in;
+//     it starts, and right behind the residuals of the sub-row the intervals are filled in wave-wide, 64 elements a trip: such a list is complete before any level runs;
 //   * which of the last W lists of a super-row the NEXT super-row copies from is read off that one's records: from the staged window
 //     when they lie in it, else from 12 bytes fetched from memory while the intervals are parsed;
 //   * flat tasks (residual segments, extras, position tasks, chunks) are dealt to lanes by a binary search over the prefix sums of the
@@ -244,15 +244,17 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
 #if defined(BVG_PROF) && defined(BVG_PROF_WORK)
     // `make work`: the same slots count WORK instead of cycles (wave-uniform counts; lane sums go through BVG_WCL):
     // {0 levels with members, 1 Z2 passes, 2 Z2 tasks, 3 Z1 passes, 4 Z2 loop steps, 5 Z2 positions, 6 residual task passes, 7 residual task-loop steps,
-    //  8 residuals decoded by tasks, 9 steps of the lane-per-node residual loop, 10 leaf chunk passes, 11 leaf loop steps (4 elements each),
-    //  12 leaf elements, 13 Z1 tasks, 14 residuals of the lane-per-node loop, 15 leaf item passes}
+    //  8 residuals decoded by tasks, 9 stored lists with reference and extras, 10 leaf chunk passes, 11 leaf loop steps (4 elements each),
+    //  12 stored lists, 13 d2 roots (stored, no reference, intervals), 14 direct roots (stored, no reference, no intervals), 15 leaf item passes}
     uint32_t cyc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t cyc2[4] = {0, 0, 0, 0};                         // round 6: {0 steps of the copy-block loop (pairs), 1 steps of the interval loop, 2 copy blocks, 3 intervals}
+    uint32_t cyc3[4] = {0, 0, 0, 0};                         // the wave-wide interval fill of the lists decoded in place: {0 lists, 1 intervals, 2 elements, 3 trips of 64 lanes}
 #define BVG_T0() 0u
 #define BVG_T1(i, t) do { (void)(t); } while (0)
 #define BVG_WC(i, n) do { cyc[i] += (uint32_t)(n); } while (0)
 #define BVG_WCL(i, n) do { cyc[i] += wave_sum32((uint32_t)(n)); } while (0)
 #define BVG_WC2(i, n) do { cyc2[i] += (uint32_t)(n); } while (0)
+#define BVG_WC3(i, n) do { cyc3[i] += (uint32_t)(n); } while (0)
 #elif defined(BVG_MARKS)
     // `hipcc -S -DBVG_MARKS`: the section boundaries as comments in the assembly (static instruction counts per section)
 #define BVG_T0() ([]() { asm volatile("; BVGMARK begin"); return 0u; }())
@@ -260,6 +262,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
 #define BVG_WC(i, n) do { } while (0)
 #define BVG_WCL(i, n) do { } while (0)
 #define BVG_WC2(i, n) do { } while (0)
+#define BVG_WC3(i, n) do { } while (0)
 #elif defined(BVG_PROF)
     uint32_t cyc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define BVG_T0() ((uint32_t)clock64())
@@ -267,12 +270,14 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
 #define BVG_WC(i, n) do { } while (0)
 #define BVG_WCL(i, n) do { } while (0)
 #define BVG_WC2(i, n) do { } while (0)
+#define BVG_WC3(i, n) do { } while (0)
 #else
 #define BVG_T0() 0u
 #define BVG_T1(i, t) do { (void)(t); } while (0)
 #define BVG_WC(i, n) do { } while (0)
 #define BVG_WCL(i, n) do { } while (0)
 #define BVG_WC2(i, n) do { } while (0)
+#define BVG_WC3(i, n) do { } while (0)
 #endif
 
     // residual skip index: entries of this block
@@ -674,7 +679,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
 #endif
         // ... and with intervals (28 % of the stored lists, 37 % of the positions the position tasks used to fill): the residuals still go
         // straight to their places -- each one shifted by the intervals that lie below it, which a task learns as it passes them -- and
-        // whoever passes an interval records where it starts; the intervals themselves are filled in by the extras pass of level 0.
+        // whoever passes an interval records where it starts; the intervals themselves are filled in wave-wide behind the sub-row's residuals.
         // (not in the 85-VGPR instantiation: its state would spill, and sparse graphs hold few intervals; on1: `stored` is set for lanes
         // behind the super-row too when the peek is unknown)
         const bool d2 = D2 && OCC <= 5 && on1 && stored && ref == 0 && ic != 0;
@@ -876,12 +881,46 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
             if (ballot(bad)) { failed = true; fail_need = kFailCode; break; }
             wave_sync();
             BVG_T1(9, tq9);
+            constexpr uint32_t HS = 16;                                       // interval entry: length | position << HS
+            const T HM = (T)0xFFFFu;
+            // ---- the intervals of the lists decoded in place (d2), WAVE-WIDE: every interval's start is on file since the wave_sync() above.  One list after the other
+            // (a wave-uniform loop, as the copy-out of the materialising form); lane k fetches entry k of the list's table, and all 64 lanes write an interval,
+            // 64 consecutive elements a trip (LongIntervalSequenceIterator.java:71-78), one multiply-add per element.  Behind it the list is complete: a chain root
+            // like a `direct` one, before any level of the sub-row runs.
+            if (D2 && OCC <= 5) {
+                const uint32_t tqf = BVG_T0();
+                uint64_t fm = ballot(act && d2);
+                if (fm) {
+                    uint64_t fsum = 0;
+                    do {
+                        const uint32_t j = (uint32_t)__ffsll((unsigned long long)fm) - 1u; fm &= fm - 1ull;
+                        const uint32_t n_ic = lane_get(ic, j), n_ib = lane_get(ib, j), n_ob = lane_get(base, j), n_d = lane_get(d, j), n_k1 = lane_get(k1, j);
+                        BVG_WC3(0, 1); BVG_WC3(1, n_ic);
+                        for (uint32_t q0 = 0; q0 < n_ic; q0 += 64) {
+                            const uint32_t q = q0 + lane, nq = n_ic - q0 < 64u ? n_ic - q0 : 64u;
+                            T e_left = 0, e_pk = 0;
+                            if (q < n_ic) { e_left = scr[n_ib + 2 * q]; e_pk = scr[n_ib + 2 * q + 1]; }
+                            for (uint32_t k = 0; k < nq; k++) {
+                                const uint32_t leftv = lane_get((uint32_t)e_left, k), pk = lane_get((uint32_t)e_pk, k);
+                                const uint32_t len = pk & (uint32_t)HM, pe = pk >> HS;
+                                if (pe + len > n_d) continue;                 // (cannot happen in a validated block; never write outside the list)
+                                BVG_WC3(2, len); BVG_WC3(3, (len + 63u) >> 6);
+                                for (uint32_t t = lane; t < len; t += 64) {
+                                    pool[n_ob + pe + t] = (T)(leftv + t);
+                                    if (!MAT) fsum += mix_node<T>(n_k1, (T)(leftv + t));
+                                }
+                            }
+                        }
+                    } while (fm);
+                    blk_chk += fsum;
+                    wave_sync();
+                }
+                BVG_T1(9, tqf);
+            }
             BVG_T1(5, tq8b);
             const uint32_t tq0 = BVG_T0();
 
             // ------------------------------------------------------------------ phase 2 of the sub-row
-            constexpr uint32_t HS = 16;                                       // interval entry: length | position << HS
-            const T HM = (T)0xFFFFu;
             uint32_t rlbN = 0, rlenS = rlenN;
             if (act && ref > 0) rlbN = nd_base[(uint32_t)(x - ref) & RM];
             // A stored node without reference is its residuals merged with its intervals (BVG:1087-1089): the parked residual values
@@ -893,11 +932,12 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
             const bool emitn = act && d > 0;
             // ---- level-synchronous emission by POSITION of the stored lists (as in bvg_rows.hip; no overlap checks: validated)
             const bool inrow = act && ref > 0 && ref + sa <= lane;                // the referenced list belongs to this sub-row
-            // A chain root that was decoded straight into place is no member of any level: a `direct` one is complete since the wave_sync() above, a `d2` one as soon
-            // as its intervals are filled in.  Who copies from such a root does not wait a level for it (with maxRef = 3 a sub-row then runs two levels, not three).
+            // A chain root that was decoded straight into place is no member of any level: a `direct` one is complete since the wave_sync() behind the residuals, a `d2`
+            // one since its intervals were filled in behind them.  Who copies from such a root does not wait a level for it (with maxRef = 3 a sub-row then runs two
+            // levels, not three).
             const bool rootdone = act && stored && ref == 0 && (direct || d2);
             const int uplane = inrow ? (int)(lane - ref) : (int)lane;
-            const uint32_t updone = (uint32_t)__shfl((int)(rootdone ? (d2 ? 2 : 1) : 0), uplane, 64);   // (executed by every lane) 2: the root still owes its intervals
+            const uint32_t updone = (uint32_t)__shfl((int)(rootdone ? 1 : 0), uplane, 64);   // (executed by every lane)
             const bool waits = inrow && updone == 0u;                         // the referenced list is built by a level of this sub-row
             uint32_t lvl = 0;
             for (int it = 0; it < 64; it++) {
@@ -906,26 +946,22 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
                 const bool ch = nl != lvl; lvl = nl;
                 if (!ballot(ch)) break;
             }
-            const bool fills = act && d2;                                     // their intervals are written by an extras pass: the one of level 0, or ...
-            // ... a pass of their own in front of the levels (kFillPass) when a list of this sub-row copies from one of them: it needs the intervals in place
-            constexpr uint32_t kFillPass = 0xFFFFFFFFu;                       // (the level counter wraps from it to level 0)
-            const bool emits = emitn && (stored || gl) && !direct && !d2;
-            const uint32_t Lfill = ballot(emits && inrow && updone == 2u) ? kFillPass : 0u;   // (a leaf is summed behind the last level: it waits for nobody)
+            const bool emits = emitn && (stored || gl) && !direct && !d2;     // (a leaf is summed behind the last level: it waits for nobody)
             if (emits) pool[rtb + nres] = sentinel<T>();                      // guard behind the node's residual positions
-            uint64_t remaining = ballot(emits || fills);
+            uint64_t remaining = ballot(emits);                               // (a sub-row whose stored lists were all decoded in place runs no level)
             wave_sync();
             BVG_T1(0, tq0);
             // WW: which of the lists with reference are built wave-wide
             const bool wwn = wwon && emits && ref > 0 && d <= kWWBits && rlenS <= kWWBits && d >= (a.dbg >> 16);   // (bits 16.. of BVG_DBG: the shortest list built this way)
             bool wwbad = false;
             uint64_t wsum = 0;
-            for (uint32_t L = Lfill; remaining; L++) {
-                const bool memall = emits && lvl == L, memf = fills && L == Lfill;
+            for (uint32_t L = 0; remaining; L++) {
+                const bool memall = emits && lvl == L;
                 const bool mem = memall && !wwn, memw = memall && wwn;
-                remaining &= ~ballot(memall || memf);
-                if (!ballot(memall || memf)) continue;
-                BVG_WC(0, L == kFillPass ? 0 : 1);                           // (the fill pass is no level: it shows as a Z1 pass)
-                if (ballot(mem || memf)) {
+                remaining &= ~ballot(memall);
+                if (!ballot(memall)) continue;
+                BVG_WC(0, 1);
+                if (ballot(mem)) {
                 // ZE: a bit vector per member (one bit per element of the list being built + a clear word behind it), all zero before the extras pass
                 uint32_t ebase = 0; bool zel = false;
                 if (zeon) {
@@ -938,9 +974,8 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
                 // ---------------- Z1: one lane per extra: its output position = (extras below it) + (copied elements below it)
                 const uint32_t tq3 = BVG_T0();
                 {
-                    const uint32_t In = mem ? nresN + ic : (memf ? ic : 0u);
-                    const bool anyf = ballot(memf) != 0;
-                    uint64_t fsum = 0;
+                    const uint32_t In = mem ? nresN + ic : 0u;
+                    uint64_t fsum = 0;                                        // (ZE only)
                     const uint32_t iincl2 = wave_incl_scan32(In), is = iincl2 - In, Itot = lane_get(iincl2, 63);
 #ifdef BVG_ABLATE_Z1
                     if (false)
@@ -961,20 +996,10 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
                             const uint32_t s_gl = (uint32_t)__shfl((int)(gl ? 1 : 0), nl, 64), g_lo = __shfl((uint32_t)gofs, nl, 64), g_hi = __shfl((uint32_t)(gofs >> 32), nl, 64);
                             t_gl = s_gl != 0; gp = a.succ + (((uint64_t)g_hi << 32) | g_lo);
                         }
-                        T vv = 0; uint32_t len = 1, pe = 0; bool isiv = false, isfill = false;
-                        uint32_t f_k1 = 0;
-                        uint32_t t_eb = 0;
-                        if (anyf || zel) {                                    // (wave-uniform: the shuffles are executed by every lane)
-                            const int s_f = __shfl((int)(memf ? 1 : 0), nl, 64);      // (hoisted: `tl && __shfl()` would run the shuffle under a lane mask)
-                            isfill = tl && s_f != 0;
-                            f_k1 = __shfl(k1, nl, 64);
-                            if (zel) t_eb = __shfl(ebase, nl, 64);
-                        }
-                        if (isfill) {                                         // an interval of a list decoded in place: its start was recorded when the residuals passed it
-                            vv = scr[t_ib + 2 * q]; const T pk = scr[t_ib + 2 * q + 1];
-                            len = (uint32_t)(pk & HM); pe = (uint32_t)(pk >> HS);
-                            if (pe + len > t_d) { pe = 0; len = 0; }
-                        } else if (tl) {
+                        T vv = 0; uint32_t len = 1, pe = 0; bool isiv = false;
+                        uint32_t z_k1 = 0, t_eb = 0;
+                        if (zel) { z_k1 = __shfl(k1, nl, 64); t_eb = __shfl(ebase, nl, 64); }   // (wave-uniform: the shuffles are executed by every lane)
+                        if (tl) {
                             uint32_t eb;
                             if (q < t_ic) {                                   // interval q: the intervals and residuals below it
                                 isiv = true;
@@ -1001,9 +1026,8 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
                         }
                         wave_sync();                                      // the parked values have been read: positions may replace them
                         if (tl && len) {
-                            if (isfill) { for (uint32_t i = 0; i < len; i++) { pool[t_ob + pe + i] = (T)(vv + i); if (!MAT) fsum += mix_node<T>(f_k1, (T)(vv + i)); } }
-                            else if (isiv && zel) {                           // ZE: the interval is written here, element by element (LongIntervalSequenceIterator.java:71-78), and its places are marked
-                                for (uint32_t i = 0; i < len; i++) { pool[t_ob + pe + i] = (T)(vv + i); fsum += mix_node<T>(f_k1, (T)(vv + i)); atomicOr(&zem[t_eb + ((pe + i) >> 5)], 1u << ((pe + i) & 31u)); }
+                            if (isiv && zel) {                                // ZE: the interval is written here, element by element (LongIntervalSequenceIterator.java:71-78), and its places are marked
+                                for (uint32_t i = 0; i < len; i++) { pool[t_ob + pe + i] = (T)(vv + i); fsum += mix_node<T>(z_k1, (T)(vv + i)); atomicOr(&zem[t_eb + ((pe + i) >> 5)], 1u << ((pe + i) & 31u)); }
                             }
                             else if (isiv) scr[t_ib + 2 * q + 1] = (T)len | (T)((T)pe << HS);
                             else {
@@ -1072,7 +1096,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
                     wave_sync();
                 }
                 blk_chk += zsum;
-                } else if (ballot(mem)) {                                      // (a pass of interval fills alone has no position task)
+                } else {
                 // ---------------- Z2: tasks of S output positions, all equally long
                 // S in one step: sum_i ceil(d_i / S) <= W / S + N - N / S < 64 once S >= W / (64 - N)  (N lists, W positions in all)
                 const uint32_t Wl = wave_sum32(mem ? d : 0u), Nl = (uint32_t)__popcll(ballot(mem));
@@ -1431,6 +1455,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
             for (int i = 12; i < 16; i++) atomicAdd(&a.acc[12 + i], (unsigned long long)cyc[i]);
 #ifdef BVG_PROF_WORK
             for (int i = 0; i < 4; i++) atomicAdd(&a.acc[28 + i], (unsigned long long)cyc2[i]);
+            for (int i = 0; i < 4; i++) atomicAdd(&a.acc[kAccStride + 4 + i], (unsigned long long)cyc3[i]);   // (the spare words of result stripe 1: stripe 0 is full)
 #endif
         }
 #endif

@@ -609,7 +609,11 @@ static int cascade(Decode& d) {
 
 static int finish(Decode& d) {
     bvg_graph* g = d.g; const DecodeArgs& a = d.a; const uint32_t lean_blocks = d.lean_blocks;
+#ifdef BVG_PROF_WORK
+    unsigned long long acc[2 * kAccStride];                 // (`make work`: the scan kernel's fill counts stand in the spare words of result stripe 1)
+#else
     unsigned long long acc[32];
+#endif
     launch_reduce_acc(g->d_acc, kAccStripes, g->stream);
     HIPCHK(hipMemcpyAsync(acc, g->d_acc, sizeof acc, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
@@ -628,9 +632,11 @@ static int finish(Decode& d) {
     }
 #else
     if ((a.dbg & 64u) && (acc[24] | acc[25] | acc[26] | acc[27]))   // only the -DBVG_PROF -DBVG_PROF_WORK build (`make work`): the slots above hold counts, not cycles
-        fprintf(stderr, "[bvg] scan kernel work: levels %llu | Z1 passes %llu tasks %llu | Z2 passes %llu tasks %llu steps %llu positions %llu | residual task passes %llu steps %llu residuals %llu, "
-                "lane-per-node steps %llu residuals %llu | leaf item passes %llu chunk passes %llu steps(x4) %llu elements %llu\n",
-                acc[9], acc[12], acc[25], acc[10], acc[11], acc[13], acc[14], acc[15], acc[16], acc[17], acc[18], acc[26], acc[27], acc[20], acc[21], acc[24]);
+        fprintf(stderr, "[bvg] scan kernel work: levels %llu | Z1 passes %llu | Z2 passes %llu tasks %llu steps %llu positions %llu | residual task passes %llu steps %llu residuals %llu | "
+                "leaf item passes %llu chunk passes %llu steps(x4) %llu | stored lists %llu: with reference and extras %llu, d2 roots %llu, direct roots %llu | "
+                "wave-wide interval fills: lists %llu intervals %llu elements %llu trips %llu\n",
+                acc[9], acc[12], acc[10], acc[11], acc[13], acc[14], acc[15], acc[16], acc[17], acc[27], acc[20], acc[21], acc[24], acc[18], acc[25], acc[26],
+                acc[kAccStride + 4], acc[kAccStride + 5], acc[kAccStride + 6], acc[kAccStride + 7]);
     if ((a.dbg & 64u) && (acc[28] | acc[29]))
         fprintf(stderr, "[bvg] scan kernel work, headers: copy-block loop steps (pairs) %llu for %llu blocks | interval loop steps %llu for %llu intervals\n", acc[28], acc[30], acc[29], acc[31]);
 #endif
