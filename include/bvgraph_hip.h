@@ -609,6 +609,59 @@ int  bvg_text_format_arcs_dev(bvg_graph* g, int64_t from, int64_t to, int64_t sh
 int  bvg_text_format_csr(int kind, int64_t first_node, int64_t nodes, const uint64_t* adj_off, const int64_t* adj, int64_t shift,
                          void* out, uint64_t cap, uint64_t* nbytes);
 
+/* ---- Transform (Transform.java, "T"): map, filter, transpose, symmetrise, union, and the lex / Gray / random permutations ----
+ * Every graph-valued call returns the CSR-in-HBM handle of the text graphs above (bvg_text): bvg_text_info / _get / _get_dev / _store /
+ * _close serve it unchanged, and a result can be the source of the next call without leaving the device.
+ * SOURCES.  bvg_transform_src names exactly one of a bvg_graph (decoded once into a CSR in HBM; its node base must be 0: BVG_E_ARG; a
+ * malformed stream gives the decode's status, a successor outside [0, nodes) BVG_E_EOF) and a bvg_text (used where it lies, never
+ * changed).  Both or neither set: BVG_E_ARG.  The two sources of bvg_transform_union must live on one device (BVG_E_ARG).
+ * Every call works on the whole CSR in HBM.  LIMITS: a source or a result of 2^31 arcs or more (the prefix sums of the pairs and the
+ * filter stages take fewer than 2^31 elements), or a permutation of 2^31 nodes or more: BVG_E_UNSUPPORTED; a map value of 2^40 or
+ * more: BVG_E_NOMEM.  *out is written on success only: every failure leaves it untouched.  The _dev twins take the caller's array in
+ * device memory.
+ *   bvg_transform_from_csr   a handle over a copy of the caller's CSR, validated as bvg_store validates its input (adj_off[0] = 0, never
+ *                            decreasing, lists strictly increasing and inside [0, nodes): else BVG_E_ARG).
+ *   bvg_transform_identity   the source as a handle of its own (a copy).
+ *   bvg_transform_map        T.mapOffline (T:1208-1269).  map_len != nodes or a value below -1: BVG_E_ARG.  -1 deletes the node and every
+ *                            arc that touches it.  The result has max(map) + 1 nodes (0 when every entry is -1; values at or beyond
+ *                            `nodes` give empty tail nodes).  Equal images merge, duplicate arcs collapse, loops created by merging stay.
+ *   bvg_transform_filter     T.filterArcs with T.NO_LOOPS (node_class must be NULL and class_len 0) or NodeClassFilter (T:154-194) with
+ *                            keepOnlySame true (SAME_CLASS: arcs between nodes of equal class stay) / false (DIFFERENT_CLASS); class_len
+ *                            must equal nodes.  The node count is unchanged.
+ *   bvg_transform_transpose  T.transposeOffline.   bvg_transform_symmetrize  T.symmetrizeOffline; with BVG_TRANSFORM_DROP_LOOPS
+ *                            T.simplifyOffline.   bvg_transform_union  T.union: max(nodes_a, nodes_b) nodes, common arcs once; with
+ *                            BVG_TRANSFORM_DROP_LOOPS the loops are dropped (T.simplify(g, t)).  Unknown flag bits: BVG_E_ARG.
+ *   bvg_transform_permutation   perm[node] = the node's new name, ready for bvg_transform_map; perm holds `nodes` entries.
+ *     BVG_PERM_LEX   the order of T:2017-2032 AS THE CODE HAS IT: the first differing position decides, a list that ends goes before one
+ *                    that continues, and otherwise the LARGER successor goes first (the comparator returns the sign of b - a; its
+ *                    javadoc says the opposite).
+ *     BVG_PERM_GRAY  the order of T:1946-1975: the same walk with parity = the position is odd.  At an even position a list that ends
+ *                    goes first, otherwise the larger successor; at an odd position the smaller successor goes first and a list that
+ *                    ends goes last.
+ *     Equal lists (the reference's quicksort leaves them in no particular order) are ordered by node id: the result is unique and one
+ *     the reference could have produced.
+ *     BVG_PERM_RANDOM  the order of (mix64(seed, node), node), the library's own sequence (not XoRoShiRo128PlusRandom's):
+ *         z = seed + (node + 1) * 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *         z = (z ^ (z >> 27)) * 0x94D049BB133111EB;    mix64 = z ^ (z >> 31)          (all in 64-bit unsigned arithmetic)
+ * DEVICE MEMORY, besides source and result: map 32 bytes per arc plus the sort's workspace; transpose 16 per arc plus the sort's;
+ * filter 12 per arc; union 12 per node; a permutation 36 bytes per node plus the sorts' workspaces.  BVG_E_NOMEM leaves nothing allocated. */
+typedef struct bvg_transform_src { bvg_graph* graph; bvg_text* csr; } bvg_transform_src;   /* exactly one non-NULL */
+enum { BVG_TRANSFORM_NO_LOOPS = 0, BVG_TRANSFORM_SAME_CLASS = 1, BVG_TRANSFORM_DIFFERENT_CLASS = 2 };
+enum { BVG_PERM_LEX = 0, BVG_PERM_GRAY = 1, BVG_PERM_RANDOM = 2 };
+#define BVG_TRANSFORM_DROP_LOOPS 1u
+int  bvg_transform_from_csr(int64_t nodes, const uint64_t* adj_off, const int64_t* adj, int device, bvg_text** out);
+int  bvg_transform_from_csr_dev(int64_t nodes, const void* d_adj_off, const void* d_adj, int device, bvg_text** out);
+int  bvg_transform_identity(const bvg_transform_src* src, bvg_text** out);
+int  bvg_transform_map(const bvg_transform_src* src, const int64_t* map, int64_t map_len, bvg_text** out);
+int  bvg_transform_map_dev(const bvg_transform_src* src, const void* d_map, int64_t map_len, bvg_text** out);
+int  bvg_transform_filter(const bvg_transform_src* src, int kind, const int64_t* node_class, int64_t class_len, bvg_text** out);
+int  bvg_transform_filter_dev(const bvg_transform_src* src, int kind, const void* d_node_class, int64_t class_len, bvg_text** out);
+int  bvg_transform_transpose(const bvg_transform_src* src, bvg_text** out);
+int  bvg_transform_symmetrize(const bvg_transform_src* src, uint32_t flags, bvg_text** out);
+int  bvg_transform_union(const bvg_transform_src* a, const bvg_transform_src* b, uint32_t flags, bvg_text** out);
+int  bvg_transform_permutation(const bvg_transform_src* src, int kind, uint64_t seed, int64_t* perm);
+int  bvg_transform_permutation_dev(const bvg_transform_src* src, int kind, uint64_t seed, void* d_perm);
+
 /* ---- synthetic-workload helper (bench only): K back-to-back copies of the graph ----
  * BV records are translation invariant (every value is coded relative to the node id, Appendix A.3
  * of SURVEY.md), so the concatenation of K copies of the bit stream is a valid BVGraph with K*nodes

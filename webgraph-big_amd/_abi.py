@@ -155,6 +155,28 @@ def text_signatures():
             "bvg_text_format_csr": [ci, i64, i64, vp, vp, i64, vp, u64, N]}
 
 
+class TransformSrc(C.Structure):
+    """bvg_transform_src: exactly one of the two handles is set."""
+    _fields_ = [("graph", C.c_void_p), ("csr", C.c_void_p)]
+
+
+# the `kind` of bvg_transform_filter and of bvg_transform_permutation, the flag of bvg_transform_symmetrize / _union
+TRANSFORM_NO_LOOPS, TRANSFORM_SAME_CLASS, TRANSFORM_DIFFERENT_CLASS = 0, 1, 2
+PERM_LEX, PERM_GRAY, PERM_RANDOM = 0, 1, 2
+TRANSFORM_DROP_LOOPS_FLAG = 1
+
+
+def transform_signatures():
+    """argtypes of the bvg_transform_* entry points (Transform), by name."""
+    vp, i64, u64, pp, ci, u32 = C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(C.c_void_p), C.c_int, C.c_uint32
+    S = C.POINTER(TransformSrc)
+    return {"bvg_transform_from_csr": [i64, vp, vp, ci, pp], "bvg_transform_from_csr_dev": [i64, vp, vp, ci, pp], "bvg_transform_identity": [S, pp],
+            "bvg_transform_map": [S, vp, i64, pp], "bvg_transform_map_dev": [S, vp, i64, pp],
+            "bvg_transform_filter": [S, ci, vp, i64, pp], "bvg_transform_filter_dev": [S, ci, vp, i64, pp],
+            "bvg_transform_transpose": [S, pp], "bvg_transform_symmetrize": [S, u32, pp], "bvg_transform_union": [S, S, u32, pp],
+            "bvg_transform_permutation": [S, ci, u64, vp], "bvg_transform_permutation_dev": [S, ci, u64, vp]}
+
+
 OK, E_ARG, E_STATE, E_UNSUPPORTED, E_IO, E_EOF, E_NOMEM, E_HIP, E_CAPACITY = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 

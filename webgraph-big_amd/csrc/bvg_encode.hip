@@ -274,6 +274,10 @@ __global__ void enc_check_kernel(const uint64_t* adj_off, const int64_t* adj, in
 
 }  // namespace
 
+void launch_csr_check(const uint64_t* d_adj_off, const int64_t* d_adj, int64_t n, unsigned* bad, hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(enc_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_adj_off, d_adj, n, bad);
+}
+
 // Device-side store: adjacency already in HBM.  d_graph_out / d_offsets_out are allocated here and released to the caller (who adopt()s them);
 // *graph_bytes = ceil(offsets[n] / 8).  Returns a bvg status.
 int encode_store_dev(const bvg_params& bp, const uint64_t* d_adj_off, const int64_t* d_adj, int64_t n, int64_t chunk_nodes, hipStream_t s,
@@ -290,7 +294,7 @@ int encode_store_dev(const bvg_params& bp, const uint64_t* d_adj_off, const int6
     HIPCHK(hipMemsetAsync(offsets, 0, (nn + 1) * sizeof(uint64_t), s));
     uint64_t total_bits = 0;
     if (n > 0) {
-        hipLaunchKernelGGL(enc_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_adj_off, d_adj, n, bad);
+        launch_csr_check(d_adj_off, d_adj, n, bad, s);
         unsigned hb = 0;
         HIPCHK(hipMemcpyAsync(&hb, bad, sizeof hb, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));

@@ -220,6 +220,16 @@ struct bvg_graph {
     }
 };
 
+// a graph as a CSR in HBM: what the text parsers (bvg_text.hip) and the transforms (bvg_transform.hip) return
+struct bvg_text {
+    int device = 0;
+    int64_t nodes = 0; uint64_t arcs = 0;
+    DevArray<uint64_t> d_off;           // adj_off[nodes + 1]
+    int64_t* d_adj = nullptr;           // adj[arcs], inside adj_base
+    DevArray<int64_t> adj_base;
+    ~bvg_text() { (void)hipSetDevice(device); }
+};
+
 namespace bvghost {
 
 // No C++ exception may cross the C ABI (a JVM behind JNI would be torn down by std::terminate): entry points that allocate
@@ -356,6 +366,10 @@ int batch_decode(bvg_graph* g, const BatchBufs& b, int64_t count, int64_t* d_suc
 // lists of 8 on shortens it further: web +11.5 %, uk +5.1 %, cnr-2000 +2.3 % over 24 / 16, for 0.1-0.3 GB of entries per GB of stream; on the dense default workload 8 / 8
 // is no faster than 16 / 16 and takes +80 % of an index that is half the stream already, on the reference-free w0 neither (its lists are residuals only: +30 % of resident
 // bytes) -- profiles/r04_skipgran3.txt.  So: 8 / 8 below 40 arcs per node (128 bits per node when the arc count is unknown) when the graph has references, else 16 / 16.
+
+// ---- bvg_text.hip: np (source, target) pairs on the device -> the CSR of `t` with `nodes` nodes (sorted, duplicates once; a pair whose ends are both
+// `nodes` is dropped).  s0 / d0 are used up.  Fewer than 2^31 pairs (BVG_E_UNSUPPORTED beyond), at most 2^40 nodes (BVG_E_NOMEM).
+int pairs_to_csr(DevArray<uint64_t>& s0, DevArray<uint64_t>& d0, uint64_t np, int64_t nodes, bvg_text* t);
 
 // ---- bvg_index_host.hip
 void skip_granularity(const Shared* sh, uint32_t& smin, uint32_t& shift);

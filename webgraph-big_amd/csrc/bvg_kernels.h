@@ -200,6 +200,9 @@ void launch_derive_offsets(const uint8_t* graph, uint64_t padded_bytes, uint64_t
 // BVGraph.store on the device (bvg_encode.hip): adjacency in CSR form (device pointers) -> .graph bytes + offsets (hipMalloc'ed here)
 int encode_store_dev(const bvg_params& p, const uint64_t* d_adj_off, const int64_t* d_adj, int64_t n, int64_t chunk_nodes, hipStream_t s,
                      uint8_t** d_graph_out, uint64_t* graph_bytes, uint64_t** d_offsets_out);
+// the check encode_store_dev runs first (bvg_transform_from_csr runs the same one): *bad != 0 when adj_off does not describe adj[0 .. adj_off[n])
+// or a list is not strictly increasing inside [0, n); *bad must be zeroed by the caller
+void launch_csr_check(const uint64_t* d_adj_off, const int64_t* d_adj, int64_t n, unsigned* bad, hipStream_t s);
 
 // synthetic workloads (bvg_tile / bvg_mosaic): the cycle {base 0, ..., base k-1} repeated
 constexpr int kMosaicMax = 16;

@@ -405,21 +405,6 @@ unsigned bits_of(uint64_t v) { return v ? 64u - (unsigned)__builtin_clzll(v) : 1
 
 int text_status(unsigned reason) { return reason == BVG_TEXT_NOT_INCREASING || reason == BVG_TEXT_SHIFT_RANGE ? BVG_E_ARG : BVG_E_IO; }
 
-}  // namespace
-}  // namespace bvghost
-
-struct bvg_text {
-    int device = 0;
-    int64_t nodes = 0; uint64_t arcs = 0;
-    DevArray<uint64_t> d_off;           // adj_off[nodes + 1]
-    int64_t* d_adj = nullptr;           // adj[arcs], inside adj_base
-    DevArray<int64_t> adj_base;
-    ~bvg_text() { (void)hipSetDevice(device); }
-};
-
-namespace bvghost {
-namespace {
-
 // fills *err from a key; the line is counted on the device (error path only)
 int refuse(const uint8_t* d_text, uint64_t key, unsigned long long* d_scratch, bvg_text_error* err) {
     const uint64_t byte = key >> 4; const unsigned reason = (unsigned)(key & 15u);
@@ -430,6 +415,48 @@ int refuse(const uint8_t* d_text, uint64_t key, unsigned long long* d_scratch, b
     if (err) { err->byte = byte; err->line = (int64_t)breaks + 1; err->reason = (int32_t)reason; err->reserved = 0; }
     return text_status(reason);
 }
+
+}  // namespace
+
+// pairs -> CSR, shared with bvg_transform.hip: np (source, target) pairs in s0 / d0 (both are used up), a pair to be dropped holding `nodes` at
+// both ends (no id reaches it, so it sorts last).  Two stable radix sorts (by target, then by source), duplicates and dropped pairs flagged,
+// a prefix sum for the positions, one lower bound per node for adj_off.  Fills t->nodes, arcs, d_off, adj.
+int pairs_to_csr(DevArray<uint64_t>& s0, DevArray<uint64_t>& d0, uint64_t np, int64_t nodes, bvg_text* t) {
+    if (nodes > kMaxNodes) return BVG_E_NOMEM;
+    t->nodes = nodes;
+    if (t->d_off.alloc((size_t)nodes + 1)) return BVG_E_NOMEM;
+    if (np == 0) {
+        HIPCHK(hipMemset(t->d_off, 0, ((size_t)nodes + 1) * sizeof(uint64_t)));
+        if (t->adj_base.alloc(1)) return BVG_E_NOMEM;
+        t->d_adj = t->adj_base; t->arcs = 0;
+        return 0;
+    }
+    if (np > 0x7FFFFFFFull) return BVG_E_UNSUPPORTED;                      // the prefix sum below takes fewer than 2^31 elements
+    DevArray<uint64_t> s1, d1, pos, ptmp; DevArray<uint8_t> stmp; DevArray<int32_t> keep;
+    if (s1.alloc(np) || d1.alloc(np)) return BVG_E_NOMEM;
+    const uint64_t drop = (uint64_t)nodes;
+    const unsigned bits = bits_of(drop);
+    size_t sb = 0;
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, sb, (const uint64_t*)d0.get(), d1.get(), (const uint64_t*)s0.get(), s1.get(), (size_t)np, 0u, bits, (hipStream_t)0));
+    if (stmp.alloc(sb)) return BVG_E_NOMEM;
+    // stable LSD: by target, then by source
+    HIPCHK(rocprim::radix_sort_pairs(stmp.get(), sb, (const uint64_t*)d0.get(), d1.get(), (const uint64_t*)s0.get(), s1.get(), (size_t)np, 0u, bits, (hipStream_t)0));
+    HIPCHK(rocprim::radix_sort_pairs(stmp.get(), sb, (const uint64_t*)s1.get(), s0.get(), (const uint64_t*)d1.get(), d0.get(), (size_t)np, 0u, bits, (hipStream_t)0));
+    stmp.reset(); s1.reset(); d1.reset();
+    if (keep.alloc(np) || pos.alloc(np + 1) || ptmp.alloc(scan_tmp_elems((int64_t)np))) return BVG_E_NOMEM;
+    hipLaunchKernelGGL(text_unique_kernel, dim3(grid((int64_t)np, 256)), dim3(256), 0, 0, s0.get(), d0.get(), np, drop, keep.get());
+    launch_exclusive_scan(keep.get(), pos.get(), (int64_t)np, ptmp.get(), nullptr);
+    uint64_t kept = 0;
+    HIPCHK(hipMemcpy(&kept, pos.get() + np, sizeof kept, hipMemcpyDeviceToHost));
+    if (t->adj_base.alloc(kept)) return BVG_E_NOMEM;
+    t->d_adj = t->adj_base; t->arcs = kept;
+    hipLaunchKernelGGL(text_compact_kernel, dim3(grid((int64_t)np, 256)), dim3(256), 0, 0, d0.get(), keep.get(), pos.get(), np, t->d_adj);
+    hipLaunchKernelGGL(text_arc_off_kernel, dim3(grid(nodes + 1, 256)), dim3(256), 0, 0, s0.get(), pos.get(), np, nodes, t->d_off.get());
+    HIPCHK(hipDeviceSynchronize());
+    return 0;
+}
+
+namespace {
 
 int parse_impl(bool arcs_mode, const uint8_t* d_text, uint64_t nbytes, int64_t shift, uint32_t flags, int64_t min_nodes, int device, bvg_text** out, bvg_text_error* err) {
     const uint64_t tiles = (nbytes + kTile - 1) / kTile, tl = tiles ? tiles : 1;
@@ -528,37 +555,14 @@ int parse_impl(bool arcs_mode, const uint8_t* d_text, uint64_t nbytes, int64_t s
     int64_t nodes = np0 ? (int64_t)top + 1 : 0;
     if (min_nodes > nodes) nodes = min_nodes;
     if (nodes > kMaxNodes) return BVG_E_NOMEM;
-    t->nodes = nodes;
-    if (t->d_off.alloc((size_t)nodes + 1)) return BVG_E_NOMEM;
-    if (np == 0) {
-        HIPCHK(hipMemset(t->d_off, 0, ((size_t)nodes + 1) * sizeof(uint64_t)));
-        if (t->adj_base.alloc(1)) return BVG_E_NOMEM;
-        t->d_adj = t->adj_base; t->arcs = 0;
-        *out = t.release();
-        return 0;
+    if (np > 0x7FFFFFFFull) return BVG_E_UNSUPPORTED;                      // the prefix sum of pairs_to_csr takes fewer than 2^31 elements
+    DevArray<uint64_t> s0, d0;
+    if (np) {
+        if (s0.alloc(np) || d0.alloc(np)) return BVG_E_NOMEM;
+        hipLaunchKernelGGL(text_pairs_kernel, dim3(grid((int64_t)np0, 256)), dim3(256), 0, 0, vals.get(), np0, sym, nol, (uint64_t)nodes, s0.get(), d0.get());
     }
-    if (np > 0x7FFFFFFFull) return BVG_E_UNSUPPORTED;                      // the prefix sum below takes fewer than 2^31 elements
-    DevArray<uint64_t> s0, d0, s1, d1, pos, ptmp; DevArray<uint8_t> stmp; DevArray<int32_t> keep;
-    if (s0.alloc(np) || d0.alloc(np) || s1.alloc(np) || d1.alloc(np)) return BVG_E_NOMEM;
-    const uint64_t drop = (uint64_t)nodes;                                 // no id reaches it
-    hipLaunchKernelGGL(text_pairs_kernel, dim3(grid((int64_t)np0, 256)), dim3(256), 0, 0, vals.get(), np0, sym, nol, drop, s0.get(), d0.get());
-    const unsigned bits = bits_of(drop);
-    size_t sb = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, sb, (const uint64_t*)d0.get(), d1.get(), (const uint64_t*)s0.get(), s1.get(), (size_t)np, 0u, bits, (hipStream_t)0));
-    if (stmp.alloc(sb)) return BVG_E_NOMEM;
-    // stable LSD: by target, then by source
-    HIPCHK(rocprim::radix_sort_pairs(stmp.get(), sb, (const uint64_t*)d0.get(), d1.get(), (const uint64_t*)s0.get(), s1.get(), (size_t)np, 0u, bits, (hipStream_t)0));
-    HIPCHK(rocprim::radix_sort_pairs(stmp.get(), sb, (const uint64_t*)s1.get(), s0.get(), (const uint64_t*)d1.get(), d0.get(), (size_t)np, 0u, bits, (hipStream_t)0));
-    if (keep.alloc(np) || pos.alloc(np + 1) || ptmp.alloc(scan_tmp_elems((int64_t)np))) return BVG_E_NOMEM;
-    hipLaunchKernelGGL(text_unique_kernel, dim3(grid((int64_t)np, 256)), dim3(256), 0, 0, s0.get(), d0.get(), np, drop, keep.get());
-    launch_exclusive_scan(keep.get(), pos.get(), (int64_t)np, ptmp.get(), nullptr);
-    uint64_t kept = 0;
-    HIPCHK(hipMemcpy(&kept, pos.get() + np, sizeof kept, hipMemcpyDeviceToHost));
-    if (t->adj_base.alloc(kept)) return BVG_E_NOMEM;
-    t->d_adj = t->adj_base; t->arcs = kept;
-    hipLaunchKernelGGL(text_compact_kernel, dim3(grid((int64_t)np, 256)), dim3(256), 0, 0, d0.get(), keep.get(), pos.get(), np, t->d_adj);
-    hipLaunchKernelGGL(text_arc_off_kernel, dim3(grid(nodes + 1, 256)), dim3(256), 0, 0, s0.get(), pos.get(), np, nodes, t->d_off.get());
-    HIPCHK(hipDeviceSynchronize());
+    const int r = pairs_to_csr(s0, d0, np, nodes, t.get());
+    if (r) return r;
     *out = t.release();
     return 0;
 }

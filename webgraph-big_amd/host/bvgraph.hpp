@@ -546,6 +546,7 @@ public:
     ~ParsedGraph() { bvg_text_close(t_); }
     int64_t numNodes() const { return n_; }
     int64_t numArcs() const { return (int64_t)m_; }
+    bvg_text* handle() const { return t_; }
     void csr(std::vector<uint64_t>& adjOff, std::vector<int64_t>& adj) const {
         adjOff.resize((size_t)n_ + 1); adj.resize((size_t)m_);
         check(bvg_text_get(t_, adjOff.data(), adjOff.size(), m_ ? adj.data() : nullptr, m_), "text_get");
@@ -597,5 +598,66 @@ inline std::string formatArcList(BVGraph& g, int64_t from, int64_t to, int64_t s
 // its own, then every node's line), the text of the arc list
 inline std::string storeASCIIGraph(BVGraph& g) { return std::to_string(g.numNodes()) + "\n" + formatASCIIGraph(g, 0, g.numNodes()); }
 inline std::string storeArcList(BVGraph& g, int64_t shift = 0) { return formatArcList(g, 0, g.numNodes(), shift); }
+
+// ---- Transform (Transform.java) over bvg_transform_*: every source is a BVGraph or a ParsedGraph, every graph-valued result a ParsedGraph
+// that stays on the device -- the source of the next call, or stored with ParsedGraph::store
+inline bvg_transform_src transformSource(BVGraph& g) { bvg_transform_src s; s.graph = g.handle(); s.csr = nullptr; return s; }
+inline bvg_transform_src transformSource(const ParsedGraph& g) { bvg_transform_src s; s.graph = nullptr; s.csr = g.handle(); return s; }
+inline std::unique_ptr<ParsedGraph> finishTransform(int st, bvg_text* t, const char* what) {
+    check(st, what);
+    return std::unique_ptr<ParsedGraph>(new ParsedGraph(t));
+}
+// a resident graph over a CSR in host memory, validated as BVGraph::store validates its input
+inline std::unique_ptr<ParsedGraph> graphFromCSR(const std::vector<uint64_t>& adjOff, const std::vector<int64_t>& adj, int device = 0) {
+    if (adjOff.empty()) throw std::invalid_argument("graphFromCSR: adjOff holds nodes + 1 entries");
+    bvg_text* t = nullptr;
+    const int st = bvg_transform_from_csr((int64_t)adjOff.size() - 1, adjOff.data(), adj.empty() ? nullptr : adj.data(), device, &t);
+    return finishTransform(st, t, "graphFromCSR");
+}
+template <class G> std::unique_ptr<ParsedGraph> identityGraph(G& g) {
+    bvg_text* t = nullptr; const bvg_transform_src s = transformSource(g);
+    const int st = bvg_transform_identity(&s, &t);
+    return finishTransform(st, t, "identityGraph");
+}
+// Transform.mapOffline: -1 deletes a node; the result has max(map) + 1 nodes
+template <class G> std::unique_ptr<ParsedGraph> mapGraph(G& g, const std::vector<int64_t>& map) {
+    bvg_text* t = nullptr; const bvg_transform_src s = transformSource(g);
+    const int st = bvg_transform_map(&s, map.empty() ? nullptr : map.data(), (int64_t)map.size(), &t);
+    return finishTransform(st, t, "mapGraph");
+}
+// Transform.filterArcs: kind = BVG_TRANSFORM_NO_LOOPS (no classes), BVG_TRANSFORM_SAME_CLASS / _DIFFERENT_CLASS (NodeClassFilter)
+template <class G> std::unique_ptr<ParsedGraph> filterArcs(G& g, int kind, const std::vector<int64_t>& nodeClass = std::vector<int64_t>()) {
+    bvg_text* t = nullptr; const bvg_transform_src s = transformSource(g);
+    const int st = bvg_transform_filter(&s, kind, nodeClass.empty() ? nullptr : nodeClass.data(), (int64_t)nodeClass.size(), &t);
+    return finishTransform(st, t, "filterArcs");
+}
+template <class G> std::unique_ptr<ParsedGraph> transposeGraph(G& g) {
+    bvg_text* t = nullptr; const bvg_transform_src s = transformSource(g);
+    const int st = bvg_transform_transpose(&s, &t);
+    return finishTransform(st, t, "transposeGraph");
+}
+// Transform.symmetrizeOffline; dropLoops: Transform.simplifyOffline
+template <class G> std::unique_ptr<ParsedGraph> symmetrizeGraph(G& g, bool dropLoops = false) {
+    bvg_text* t = nullptr; const bvg_transform_src s = transformSource(g);
+    const int st = bvg_transform_symmetrize(&s, dropLoops ? BVG_TRANSFORM_DROP_LOOPS : 0u, &t);
+    return finishTransform(st, t, "symmetrizeGraph");
+}
+template <class G> std::unique_ptr<ParsedGraph> simplifyGraph(G& g) { return symmetrizeGraph(g, true); }
+// Transform.union; dropLoops: Transform.simplify(g, t)
+template <class A, class B> std::unique_ptr<ParsedGraph> unionGraphs(A& a, B& b, bool dropLoops = false) {
+    bvg_text* t = nullptr; const bvg_transform_src sa = transformSource(a), sb = transformSource(b);
+    const int st = bvg_transform_union(&sa, &sb, dropLoops ? BVG_TRANSFORM_DROP_LOOPS : 0u, &t);
+    return finishTransform(st, t, "unionGraphs");
+}
+// perm[node] = the node's new name (kind = BVG_PERM_LEX / BVG_PERM_GRAY / BVG_PERM_RANDOM), ready for mapGraph
+template <class G> std::vector<int64_t> permutation(G& g, int kind, uint64_t seed = 0) {
+    std::vector<int64_t> perm((size_t)g.numNodes());
+    const bvg_transform_src s = transformSource(g);
+    check(bvg_transform_permutation(&s, kind, seed, perm.empty() ? nullptr : perm.data()), "permutation");
+    return perm;
+}
+template <class G> std::vector<int64_t> lexicographicalPermutation(G& g) { return permutation(g, BVG_PERM_LEX); }
+template <class G> std::vector<int64_t> grayCodePermutation(G& g) { return permutation(g, BVG_PERM_GRAY); }
+template <class G> std::vector<int64_t> randomPermutation(G& g, uint64_t seed) { return permutation(g, BVG_PERM_RANDOM, seed); }
 
 }  // namespace webgraph
