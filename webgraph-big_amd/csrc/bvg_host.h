@@ -132,6 +132,11 @@ struct SkipIndex {
     uint64_t gen = 0;                         // identity of this snapshot: what a handle learned about blocks (tier lists, lean / row split) holds for ONE snapshot only
     std::vector<uint64_t> h_first;            // nblk + 1 entry indices (host copy: index_bytes of a range)
     std::vector<uint8_t> h_fmt;               // host copy of d_fmt: 1 = validated by the row kernel (the lean scan kernel may take the block)
+    // recorded positions of the scan kernel's extras (DecodeArgs::pos_*; count_positions, bvg_index_host.hip): counted with the index, written by the first scans of every
+    // block (pos_ready), never saved -- loading an index counts them again.  They live BEHIND the skip index's own data in its four arrays (the bit per node in
+    // d_val, the per-block bases in d_first, the entries in d_bit, the flags in d_fmt): these point there.  nullptr: the scan kernel searches for the positions as before.
+    uint32_t* pos_refd = nullptr; uint64_t* pos_first = nullptr; uint16_t* pos_ent = nullptr; uint8_t* pos_ready = nullptr;
+    std::vector<uint64_t> h_pos_first;        // nblk + 1 entry indices (host copy: index_bytes of a range); empty = no recorded positions
     SkipIndex() = default; SkipIndex(const SkipIndex&) = delete; SkipIndex& operator=(const SkipIndex&) = delete;
     ~SkipIndex() { (void)hipSetDevice(device); }
 };

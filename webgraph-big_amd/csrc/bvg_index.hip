@@ -32,6 +32,43 @@ template <bool GEN> struct Rdi {   // the field readers of bvg_kernels.hip (GEN 
     static __device__ __forceinline__ uint64_t residual(BitCursor& c, const Codings& k, uint64_t g) { if (GEN) return c.read_coded(k.residual, (unsigned)k.zeta_k, g); return c.read_zeta((unsigned)k.zeta_k, g); }
 };
 
+// The header of a record of outdegree d > 0 behind its outdegree (BVG:1010-1060): the reference, the copy blocks and the intervals only as far as their sums go, which
+// gives the residual count and leaves the cursor on the first residual code.  nd_d: the outdegrees of the W nodes before x (node id mod kRing).  Returns `ok`.
+template <bool GEN>
+__device__ __forceinline__ bool parse_header(BitCursor& cur, const DecodeArgs& a, int64_t x, uint64_t rec_end, uint32_t d, const uint32_t* nd_d, bool ok, uint32_t& ref, uint32_t& ic, uint32_t& nres) {
+    typedef Rdi<GEN> R;
+    const int W = a.window;
+    ref = 0; ic = 0;
+    if (W > 0) { const uint64_t rv = R::reference(cur, a.cod, rec_end); if (rv > (uint64_t)W || (int64_t)rv > x) ok = false; else ref = (uint32_t)rv; }
+    int64_t extra = d;
+    if (ref > 0) {
+        uint64_t nb = R::block_count(cur, a.cod, rec_end);
+        if (nb > rec_end - (cur.pos < rec_end ? cur.pos : rec_end) + 1) { ok = false; nb = 0; }
+        int64_t copied = 0, tot = 0;
+        for (uint64_t i = 0; i < nb; i++) {
+            const int64_t b = (int64_t)R::block(cur, a.cod, rec_end) + (i ? 1 : 0);
+            tot += b; if (!(i & 1)) copied += b;
+            if (cur.pos > rec_end) { ok = false; break; }
+        }
+        if (!(nb & 1)) copied += (int64_t)nd_d[(uint32_t)(x - ref) & RM] - tot;           // BVG:1030
+        extra = (int64_t)d - copied;
+        if (extra < 0 || copied < 0) { ok = false; extra = 0; }
+    }
+    if (extra > 0 && a.min_interval != 0) {                                              // always gamma (BVG:1040-1058)
+        uint64_t ni = cur.read_gamma(rec_end);
+        if (ni > (rec_end - (cur.pos < rec_end ? cur.pos : rec_end)) / 2 + 1) { ok = false; ni = 0; }
+        for (uint64_t i = 0; i < ni; i++) {
+            (void)cur.read_gamma(rec_end);
+            extra -= (int64_t)cur.read_gamma(rec_end) + a.min_interval;
+            if (cur.pos > rec_end) { ok = false; break; }
+        }
+        if (extra < 0) { ok = false; extra = 0; }
+        ic = ok ? (uint32_t)ni : 0u;
+    }
+    nres = ok ? (uint32_t)extra : 0u;
+    return ok;
+}
+
 // T: the type of the entries' values (uint32_t, or uint64_t for an index built by the 64-bit kernels)
 template <typename T, bool GEN>
 __global__ void __launch_bounds__(64) index_walk_kernel(DecodeArgs a) {
@@ -49,7 +86,6 @@ __global__ void __launch_bounds__(64) index_walk_kernel(DecodeArgs a) {
     if (sk_n == 0) return;                                              // no list of this block has entries
     const uint32_t halo = a.blk_halo[bid];
     const uint64_t hmask = a.blk_mask[bid];
-    const int W = a.window;
     const int64_t hs = s - (int64_t)halo;
     for (unsigned i = lane; i < (unsigned)kRing; i += 64) nd_d[i] = 0;
     // the block's stream (halo included) in LDS, big-endian dwords: a block is ~4 KiB; what does not fit the window is read from global memory (BitCursor::peek)
@@ -114,36 +150,8 @@ __global__ void __launch_bounds__(64) index_walk_kernel(DecodeArgs a) {
         if (needed) { const uint64_t dv = R::outdegree(cur, a.cod, rec_end); ok = dv <= 0x7FFFFFFFull; d = ok ? (uint32_t)dv : 0u; }
         if (needed) nd_d[(uint32_t)x & RM] = d;
         __syncthreads();
-        uint32_t nres = 0;
-        if (needed && d > 0) {
-            uint32_t ref = 0;
-            if (W > 0) { const uint64_t rv = R::reference(cur, a.cod, rec_end); if (rv > (uint64_t)W || (int64_t)rv > x) ok = false; else ref = (uint32_t)rv; }
-            int64_t extra = d;
-            if (ref > 0) {
-                uint64_t nb = R::block_count(cur, a.cod, rec_end);
-                if (nb > rec_end - (cur.pos < rec_end ? cur.pos : rec_end) + 1) { ok = false; nb = 0; }
-                int64_t copied = 0, tot = 0;
-                for (uint64_t i = 0; i < nb; i++) {
-                    const int64_t b = (int64_t)R::block(cur, a.cod, rec_end) + (i ? 1 : 0);
-                    tot += b; if (!(i & 1)) copied += b;
-                    if (cur.pos > rec_end) { ok = false; break; }
-                }
-                if (!(nb & 1)) copied += (int64_t)nd_d[(uint32_t)(x - ref) & RM] - tot;           // BVG:1030
-                extra = (int64_t)d - copied;
-                if (extra < 0 || copied < 0) { ok = false; extra = 0; }
-            }
-            if (extra > 0 && a.min_interval != 0) {                                              // always gamma (BVG:1040-1058)
-                uint64_t ni = cur.read_gamma(rec_end);
-                if (ni > (rec_end - (cur.pos < rec_end ? cur.pos : rec_end)) / 2 + 1) { ok = false; ni = 0; }
-                for (uint64_t i = 0; i < ni; i++) {
-                    (void)cur.read_gamma(rec_end);
-                    extra -= (int64_t)cur.read_gamma(rec_end) + a.min_interval;
-                    if (cur.pos > rec_end) { ok = false; break; }
-                }
-                if (extra < 0) { ok = false; extra = 0; }
-            }
-            nres = ok ? (uint32_t)extra : 0u;
-        }
+        uint32_t nres = 0, ref = 0, ic = 0;
+        if (needed && d > 0) ok = parse_header<GEN>(cur, a, x, rec_end, d, nd_d, ok, ref, ic, nres);
         const uint32_t cntE = (needed && d > 0 && ok && nres >= kSkipMin) ? (nres - 1u) >> kSkipShift : 0u;
         uint32_t eincl = cntE;
 #pragma unroll
@@ -164,6 +172,57 @@ __global__ void __launch_bounds__(64) index_walk_kernel(DecodeArgs a) {
     if (qn) walk();
 }
 
+// ---- recorded positions (bvg_scan.hip): what is counted once per index ----
+// Which nodes some later node copies from: a thread per node y of [from, to) reads its outdegree (gamma) and its reference (unary) and sets bit y - ref.  Exact, where
+// the scan kernel's own `copied_from` is conservative (an unknown peek, a super-row cut short) and blind to the next block.
+__global__ void __launch_bounds__(256) pos_refd_kernel(const uint8_t* graph, uint64_t limit_byte, Offsets offsets, int64_t from, int64_t to, int window, uint32_t* refd) {
+    const int64_t y = from + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (y >= to) return;
+    const uint64_t rec_end = offsets[y + 1];
+    BitCursor cur{graph, offsets[y], limit_byte};
+    if (cur.read_gamma(rec_end) == 0 || cur.pos > rec_end) return;
+    const uint64_t ref = cur.read_unary(rec_end);
+    if (ref == 0 || ref > (uint64_t)window || (int64_t)ref > y) return;
+    const uint64_t x = (uint64_t)y - ref;
+    atomicOr(&refd[x >> 5], 1u << (x & 31u));
+}
+
+// The entries of every block: one wavefront per block parses the record headers of the nodes the block decodes (its halo included, as the scan kernel does: a lane per
+// record) and sums what scan_kernel counts -- nres + ic for a list with reference, ic for one without, when the node's bit is set and 0 < d < 0xFFFF.
+__global__ void __launch_bounds__(64) pos_count_kernel(DecodeArgs a) {
+    __shared__ uint32_t nd_d[kRing];
+    const unsigned lane = threadIdx.x;
+    const uint32_t bid = a.blk_lo + blockIdx.x;
+    const int64_t s = (int64_t)a.blk_first[bid], e = (int64_t)a.blk_first[bid + 1];
+    if (s >= e) { if (lane == 0) a.pos_cnt[bid] = 0; return; }
+    const uint32_t halo = a.blk_halo[bid];
+    const uint64_t hmask = a.blk_mask[bid];
+    const int64_t hs = s - (int64_t)halo;
+    for (unsigned i = lane; i < (unsigned)kRing; i += 64) nd_d[i] = 0;
+    __syncthreads();
+    uint32_t total = 0;
+    for (int64_t r0 = hs; r0 < e; r0 += 64) {
+        const int64_t x = r0 + lane;
+        const uint64_t hbit = x < s ? (uint64_t)(s - 1 - x) & 63u : 0;
+        const bool needed = x < e && (x >= s || ((hmask >> hbit) & 1ull));
+        uint64_t off_x = 0, rec_end = 0;
+        if (needed) { off_x = a.offsets[x]; rec_end = a.offsets[x + 1]; }
+        BitCursor cur{a.graph, off_x, a.limit_byte};
+        uint32_t d = 0;
+        bool ok = needed;
+        if (needed) { const uint64_t dv = cur.read_gamma(rec_end); ok = dv <= 0x7FFFFFFFull; d = ok ? (uint32_t)dv : 0u; }
+        if (needed) nd_d[(uint32_t)x & RM] = d;
+        __syncthreads();
+        uint32_t nres = 0, ref = 0, ic = 0;
+        if (needed && d > 0) ok = parse_header<false>(cur, a, x, rec_end, d, nd_d, ok, ref, ic, nres);
+        const bool refd = needed && ((a.pos_refd[(uint64_t)x >> 5] >> ((uint32_t)x & 31u)) & 1u) != 0;
+        total += (refd && ok && d > 0 && d < 0xFFFFu) ? (ref > 0 ? nres + ic : ic) : 0u;
+        __syncthreads();
+    }
+    total = wave_sum32(total);
+    if (lane == 0) a.pos_cnt[bid] = total;
+}
+
 // Entries of blocks that no kernel finished with a mark (fmt 0: they ended in the generic kernel, which uses none) are never read; the dense walk may have
 // written some before the block failed over.  They are cleared, so that an index -- and its file -- does not depend on how it was built.
 __global__ void __launch_bounds__(256) clear_unmarked_entries_kernel(const uint64_t* first, const uint8_t* fmt, uint16_t* bit, void* val, uint32_t blo, uint32_t bhi, int wide) {
@@ -173,6 +232,15 @@ __global__ void __launch_bounds__(256) clear_unmarked_entries_kernel(const uint6
 }
 
 }  // namespace
+
+void launch_pos_refd(const uint8_t* graph, uint64_t limit_byte, Offsets offsets, int64_t from, int64_t to, int window, uint32_t* refd, hipStream_t s) {
+    if (to <= from || window <= 0) return;
+    hipLaunchKernelGGL(pos_refd_kernel, dim3((unsigned)((to - from + 255) / 256)), dim3(256), 0, s, graph, limit_byte, offsets, from, to, window, refd);
+}
+void launch_pos_count(const DecodeArgs& a, uint32_t nblocks, hipStream_t s) {
+    if (nblocks == 0) return;
+    hipLaunchKernelGGL(pos_count_kernel, dim3(nblocks), dim3(64), 0, s, a);
+}
 
 void launch_clear_unmarked_entries(const uint64_t* first, const uint8_t* fmt, uint16_t* bit, void* val, uint32_t blo, uint32_t bhi, bool wide, hipStream_t s) {
     if (bhi <= blo) return;

@@ -22,6 +22,33 @@ void skip_granularity(const Shared* sh, uint32_t& smin, uint32_t& shift) {
     }
 }
 
+// The recorded positions of the scan kernel's extras (DecodeArgs::pos_*, bvg_scan.hip), counted once per index: the bit per node "some later node copies from it" (into
+// `refd`, zeroed by the caller) and the entries of every block of [blo, bhi) by a header walk (into `cnt_d`), then their exclusive prefix `first`.  The arrays themselves are
+// the tails of the skip index's own (build_skip): same snapshot, range, generation and owner.  Not saved in basename.bvgidx.  Best effort: false = none (other codings, no
+// references, a marks-only handle, BVG_NO_POS=1, a HIP error), and the index is as good as it was.
+static bool positions_wanted(const bvg_graph* g) {
+    const Shared* sh = g->sh; const int W = sh->p.window_size;
+    return W > 0 && W <= kMaxWindow && is_default_codings(codings_of(sh->p)) && g->tun.no_index != 2 && !(knob("BVG_NO_POS") && atoi(knob("BVG_NO_POS")));
+}
+static bool count_positions(bvg_graph* g, const Plan& pl, uint32_t blo, uint32_t bhi, uint32_t* cnt_d, uint32_t* refd, std::vector<uint64_t>& first) {
+    Shared* sh = g->sh;
+    const uint32_t nblk = pl.nblk; const int W = sh->p.window_size; const int64_t n = sh->p.nodes;
+    // every node that a block of the range decodes (the first block's halo) and every node that copies from one (the W nodes behind the range)
+    const int64_t rfrom = std::max<int64_t>((int64_t)pl.h_first[blo] - kMaxHalo, 0), rto = std::min<int64_t>((int64_t)pl.h_first[bhi] + W, n);
+    launch_pos_refd(sh->d_graph, sh->nbytes, sh->offs, rfrom, rto, W, refd, g->stream);
+    DecodeArgs ca{};
+    ca.graph = sh->d_graph; ca.limit_byte = sh->nbytes; ca.padded_bytes = sh->padded; ca.offsets = sh->offs; ca.n = n;
+    ca.blk_first = pl.d_first; ca.blk_halo = pl.d_halo; ca.blk_mask = pl.d_mask; ca.blk_lo = blo;
+    ca.window = W; ca.min_interval = sh->p.min_interval_length; ca.cod = codings_of(sh->p);
+    ca.pos_refd = refd; ca.pos_cnt = cnt_d;
+    launch_pos_count(ca, bhi - blo, g->stream);
+    std::vector<uint32_t> cnt(nblk);
+    if (hipStreamSynchronize(g->stream) != hipSuccess || hipMemcpy(cnt.data(), cnt_d, (size_t)nblk * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return false; }
+    first.assign(nblk + 1, 0);
+    for (uint32_t i = 0; i < nblk; i++) first[i + 1] = first[i] + ((i >= blo && i < bhi) ? cnt[i] : 0u);
+    return true;
+}
+
 // Residual skip index: nodes with long residual lists get one entry per kSkipEvery residuals, so the row kernel can decode a
 // long list as independent segments on otherwise idle lanes.  Two passes of the ordinary decode over the plan blocks [blo, bhi):
 // count the entries of every block, prefix-sum on the host, fill.  An index, not a cache: every gap is still decoded from the stream.
@@ -82,7 +109,10 @@ int build_skip(bvg_graph* g, const std::shared_ptr<Plan>& plp, uint32_t blo, uin
     DevArray<uint32_t> cnt_d;
     const auto tb0 = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - tb0).count(); };
-    if (cnt_d.alloc(nblk) || hipMemset(cnt_d, 0, (size_t)nblk * sizeof(uint32_t)) != hipSuccess) return give_up(SkipIndex::kResources);
+    // (behind the entry counts of the skip index: those of the recorded positions and the bit per node they follow from)
+    bool pos = positions_wanted(g);
+    const size_t pwords = pos ? (size_t)((sh->p.nodes + 31) >> 5) + 1 : 0, cnt_n = (size_t)nblk * (pos ? 2 : 1) + pwords;
+    if (cnt_d.alloc(cnt_n) || hipMemset(cnt_d, 0, cnt_n * sizeof(uint32_t)) != hipSuccess) return give_up(SkipIndex::kResources);
     g->skip_mode = 1; g->skip_cnt = cnt_d; g->skip_building = ix;          // (the counting pass counts in the new index's granularity)
     int r = run_decode(g, nfrom, nto, false, nullptr, nullptr, nullptr, nullptr, nullptr, &plp);
     g->skip_mode = 0; g->skip_cnt = nullptr; g->skip_building.reset();
@@ -93,11 +123,24 @@ int build_skip(bvg_graph* g, const std::shared_ptr<Plan>& plp, uint32_t blo, uin
     std::vector<uint64_t> first(nblk + 1, 0);
     for (uint32_t i = 0; i < nblk; i++) first[i + 1] = first[i] + ((i >= blo && i < bhi) ? cnt[i] : 0u);
     const uint64_t total = first[nblk];
-    if (ix->d_first.alloc((size_t)nblk + 1) || ix->d_bit.alloc(total + 8) || ix->d_fmt.alloc(nblk) || hipMemset(ix->d_fmt, 0, nblk) != hipSuccess ||
-        ix->d_val.alloc(total * (build_wide ? sizeof(uint64_t) : sizeof(uint32_t)) + 16)) return give_up(SkipIndex::kResources);   // (16 bytes behind the entries of either array)
+    std::vector<uint64_t> pfirst;
+    pos = pos && count_positions(g, pl, blo, bhi, cnt_d + nblk, cnt_d + 2 * (size_t)nblk, pfirst);
+    const uint64_t ptotal = pos ? pfirst[nblk] : 0;
+    const size_t val_bytes = total * (build_wide ? sizeof(uint64_t) : sizeof(uint32_t)) + 16;                 // (16 bytes behind the entries of either array)
+    // the recorded positions behind the index's own data, array by array: bases, entries (+ 8), flags, the bit per node
+    if (ix->d_first.alloc(((size_t)nblk + 1) * (pos ? 2 : 1)) || ix->d_bit.alloc(total + 8 + (pos ? ptotal + 8 : 0)) || ix->d_fmt.alloc((size_t)nblk * (pos ? 2 : 1)) ||
+        hipMemset(ix->d_fmt, 0, (size_t)nblk * (pos ? 2 : 1)) != hipSuccess || ix->d_val.alloc(val_bytes + (pos ? pwords * sizeof(uint32_t) : 0))) return give_up(SkipIndex::kResources);
     if (hipMemcpy(ix->d_first, first.data(), (size_t)(nblk + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) return give_up(SkipIndex::kResources);
     // (entries nobody fills -- the allotment of a block that ends in the generic kernel -- read as zero: an index, and its file, are reproducible)
-    if (hipMemsetAsync(ix->d_bit, 0, total * sizeof(uint16_t) + 16, g->stream) != hipSuccess || hipMemsetAsync(ix->d_val, 0, total * (build_wide ? sizeof(uint64_t) : sizeof(uint32_t)) + 16, g->stream) != hipSuccess) return give_up(SkipIndex::kResources);
+    if (hipMemsetAsync(ix->d_bit, 0, ix->d_bit.count() * sizeof(uint16_t), g->stream) != hipSuccess || hipMemsetAsync(ix->d_val, 0, val_bytes, g->stream) != hipSuccess) return give_up(SkipIndex::kResources);
+    if (pos) {
+        ix->pos_first = ix->d_first + nblk + 1; ix->pos_ent = ix->d_bit + total + 8; ix->pos_ready = ix->d_fmt + nblk; ix->pos_refd = reinterpret_cast<uint32_t*>(ix->d_val.get() + val_bytes);
+        if (hipMemcpy(ix->pos_first, pfirst.data(), (size_t)(nblk + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemsetAsync(ix->pos_ent, 0xFF, (ptotal + 8) * sizeof(uint16_t), g->stream) != hipSuccess ||      // (0xFFFF: nobody has written this entry; no position is that large)
+            hipMemcpyAsync(ix->pos_refd, cnt_d + 2 * (size_t)nblk, pwords * sizeof(uint32_t), hipMemcpyDeviceToDevice, g->stream) != hipSuccess) return give_up(SkipIndex::kResources);
+        ix->h_pos_first.swap(pfirst);
+        if (dbg_on()) fprintf(stderr, "[bvg] recorded positions: blocks [%u, %u), %llu entries, %.1f MiB + %.1f MiB of node bits\n", blo, bhi, (unsigned long long)ptotal, (double)ptotal * 2.0 / 1048576.0, (double)pwords * 4.0 / 1048576.0);
+    }
     ix->total = total;
     const double t_alloc = since();
     // Filling: a DENSE WALK writes the entries (bvg_index.hip: one lane per long list, the lists of a block queued together), then the validating pass decodes every block
@@ -146,6 +189,8 @@ int build_skip(bvg_graph* g, const std::shared_ptr<Plan>& plp, uint32_t blo, uin
 // record (window, minimum interval length, zeta k, the five codings), and a checksum over the whole payload; every array is range-checked
 // on the way in (halo lengths, marks, monotone entry counts, sizes).  A file that fails any of it is refused (BVG_E_IO) and the index is
 // built from the stream as usual.
+// The recorded positions of the scan kernel's extras (count_positions above) are NOT in the file: loading counts them again (a header walk, as in build_skip) and the
+// blocks of a loaded index record on their first scans.
 struct IndexHeader {
     char magic[8]; uint32_t version, block_bits; uint64_t graph_bytes, total_bits; int64_t nodes; uint64_t stream_hash;
     uint32_t window, wide, nblk, has_skip, skip_lo, skip_hi; uint64_t skip_total;
@@ -306,7 +351,25 @@ int load_index_impl(bvg_graph* g, const char* path) {
         }
         acc = fold_hash(acc, host_hash(ix->h_first.data(), (nb + 1) * 8), 5); acc = fold_hash(acc, host_hash(ix->h_fmt.data(), nb), 6);
         const size_t vb = ix->wide ? 8 : 4;
-        if (ix->d_first.alloc(nb + 1) || ix->d_bit.alloc((size_t)ix->total + 8) || ix->d_fmt.alloc(nb) || ix->d_val.alloc((size_t)ix->total * vb + 16)) return BVG_E_NOMEM;
+        // The recorded positions are not in the file, but what they need is counted here as in build_skip (same tails of the same four arrays, no allocation of
+        // their own), so the blocks of a loaded index record on their first scan.  The per-block counts stand where the bases go until those are known.
+        bool pos = positions_wanted(g);
+        const size_t pwords = pos ? (size_t)((sh->p.nodes + 31) >> 5) + 1 : 0, val_bytes = (size_t)ix->total * vb + 16;
+        if (ix->d_first.alloc((nb + 1) * (pos ? 2 : 1)) || ix->d_fmt.alloc(nb * (pos ? 2 : 1)) || ix->d_val.alloc(val_bytes + pwords * sizeof(uint32_t))) return BVG_E_NOMEM;
+        std::vector<uint64_t> pfirst;
+        if (pos) {
+            uint32_t* const refd = reinterpret_cast<uint32_t*>(ix->d_val.get() + val_bytes); uint32_t* const cnt = reinterpret_cast<uint32_t*>(ix->d_first.get() + nb + 1);
+            HIPCHK(hipMemsetAsync(refd, 0, pwords * sizeof(uint32_t), g->stream)); HIPCHK(hipMemsetAsync(cnt, 0, nb * sizeof(uint32_t), g->stream));
+            pos = count_positions(g, pl, ix->blk_lo, ix->blk_hi, cnt, refd, pfirst);
+        }
+        const uint64_t ptotal = pos ? pfirst[nb] : 0;
+        if (ix->d_bit.alloc((size_t)ix->total + 8 + (pos ? ptotal + 8 : 0))) return BVG_E_NOMEM;
+        if (pos) {
+            ix->pos_first = ix->d_first + nb + 1; ix->pos_ent = ix->d_bit + ix->total + 8; ix->pos_ready = ix->d_fmt + nb; ix->pos_refd = reinterpret_cast<uint32_t*>(ix->d_val.get() + val_bytes);
+            HIPCHK(hipMemcpy(ix->pos_first, pfirst.data(), (nb + 1) * 8, hipMemcpyHostToDevice));
+            HIPCHK(hipMemset(ix->pos_ent, 0xFF, (ptotal + 8) * sizeof(uint16_t))); HIPCHK(hipMemset(ix->pos_ready, 0, nb));
+            ix->h_pos_first.swap(pfirst);
+        }
         HIPCHK(hipMemcpy(ix->d_first, ix->h_first.data(), (nb + 1) * 8, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(ix->d_fmt, ix->h_fmt.data(), nb, hipMemcpyHostToDevice));
         if (!get_dev(f, ix->d_bit, (size_t)ix->total * 2) || !get_dev(f, ix->d_val, (size_t)ix->total * vb)) return BVG_E_IO;

@@ -114,7 +114,16 @@ struct DecodeArgs {
     uint8_t* skip_fmt;                  // per block: who filled its entries (skip_mode 2) -- 1 = row kernels (one slot per entry), 2 = the giant
                                         // kernel (two slots per entry: 32-bit offsets); a kernel uses only entries of its own format
     uint32_t skip_mode;
-    uint32_t xcds;                      // XCDs the work order is laid out for (8 on MI355X; 1 = plain order): xcd_order(), bvg_rows_common.h
+    // recorded positions (scan_kernel, scan mode): the output position of every extra -- the intervals of a node first, then its residuals -- of every list
+    // that some later node of the graph copies from (bit x of pos_refd) and that holds fewer than 0xFFFF elements; nres + ic entries with a reference, ic
+    // without.  Entries of a block (halo included) are contiguous, in node order, from pos_first[bid] on; pos_ready[bid]: bit 0 = the entries of the lists
+    // with reference are on file, bit 1 = those of the lists without too.  They depend on the stream and the block plan alone, so every geometry shares them.
+    const uint32_t* pos_refd;           // a bit per node of the graph, or nullptr
+    const uint64_t* pos_first;          // nblk+1 entry indices, or nullptr = no recorded positions
+    uint16_t* pos_ent; uint8_t* pos_ready;
+    uint32_t pos_stat;                  // 1 = count the blocks that ran recorded / recording (BVG_DEBUG): the spare words 4 / 5 of result stripe 2
+    uint32_t* pos_cnt;                  // pos_count_kernel: per-block entry count out
+    uint32_t xcds;                     // XCDs the work order is laid out for (8 on MI355X; 1 = plain order): xcd_order(), bvg_rows_common.h
     uint32_t flat_recs;                 // flat scan kernel (experimental/bvg_flat.hip): records per super-row (a multiple of 64: 64 on dense graphs, up to 256 on sparse ones)
 };
 
@@ -164,6 +173,10 @@ void launch_giant_decode(const DecodeArgs& a, uint32_t nblocks, bool wide, bool 
 // sums the result stripes into stripe 0 (one workgroup)
 // the filling pass of the skip index as a dense walk (bvg_index.hip): entries of the blocks of the work list, where the counting pass allotted them
 void launch_index_walk(const DecodeArgs& a, uint32_t nblocks, bool wide, hipStream_t s);
+// recorded positions, run once per index (bvg_index.hip): which nodes of [from, to) some later node copies from (a bit per node of the graph, zeroed by the caller),
+// and the entries per block that follow from them (a.pos_refd in, a.pos_cnt out; default codings)
+void launch_pos_refd(const uint8_t* graph, uint64_t limit_byte, Offsets offsets, int64_t from, int64_t to, int window, uint32_t* refd, hipStream_t s);
+void launch_pos_count(const DecodeArgs& a, uint32_t nblocks, hipStream_t s);
 void launch_clear_unmarked_entries(const uint64_t* first, const uint8_t* fmt, uint16_t* bit, void* val, uint32_t blo, uint32_t bhi, bool wide, hipStream_t s);
 void launch_reduce_acc(unsigned long long* acc, uint32_t stripes, hipStream_t s);
 // *out += position-keyed 64-bit hash of the nbytes at p (device memory, 8-byte aligned); *out must be zeroed by the caller

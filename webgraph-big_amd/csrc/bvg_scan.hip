@@ -284,6 +284,20 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
     const uint64_t sk_base = a.skip_first[bid];
     const uint32_t sk_n = (uint32_t)(a.skip_first[bid + 1] - sk_base);
     uint32_t sk_run = 0;
+    // recorded positions (DecodeArgs::pos_*): where every extra -- interval or residual -- of a stored list goes in the list depends on the stream alone, so it is
+    // searched for once (Z1 below) and read back ever after.  A block whose flag is clear runs Z1 as always and writes each position down; when the block ends well,
+    // the flag is set.  A block whose flag is set places ALL extras of a sub-row in one pass in front of its levels, and the levels run Z2 only.  Lists decoded in
+    // place (d2) are no members of a level: an instantiation with them needs the entries of the lists with reference only (bit 0), one without needs both bits.
+    constexpr uint32_t kPosNeed = (D2 && OCC <= 5) ? 1u : 3u;
+    const bool posm = !MAT && a.pos_first != nullptr && !wwon && !zeon;
+    uint64_t ps_base = 0; uint32_t ps_n = 0, ps_run = 0;
+    bool pos_use = false;
+    if (posm) {
+        ps_base = a.pos_first[bid]; ps_n = (uint32_t)(a.pos_first[bid + 1] - ps_base);
+        const uint32_t fl = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)__hip_atomic_load(&a.pos_ready[bid], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT));
+        pos_use = (fl & kPosNeed) == kPosNeed;
+    }
+    const bool pos_rec = posm && !pos_use;
 
     // keeps only the stored lists of the W nodes before node `upto`, moved to the front of the pool
     auto compact = [&](int64_t upto) {
@@ -359,7 +373,9 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
             const int64_t nx = r0 + K1 + lane;
             if (nx < e) { nxt_off = a.offsets[nx]; nxt_end = a.offsets[nx + 1]; }
         }
-        uint32_t rel = (uint32_t)(off_x - stg_bit0);                          // bit cursor relative to the window
+        uint32_t refw = 0;                                                    // recorded positions: the word that holds this node's "copied from" bit
+        if (posm && in_range) refw = a.pos_refd[(uint64_t)x >> 5];
+        uint32_t rel = (uint32_t)(off_x - stg_bit0);                         // bit cursor relative to the window
         const uint32_t pend = (uint32_t)(rec_end - stg_bit0);
         const uint32_t recrel = rel;
         bool bad = false;
@@ -609,7 +625,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
         // The last W nodes of the super-row can be referenced by the first W nodes of the next one: peek at those records' references
         // (outdegree gamma, reference unary: BVG:654-660, 692-703) when they lie inside the staged window; otherwise, assume they are.
         // Nodes of the next BLOCK do not count: that block decodes its halo itself.
-        uint64_t nextmask = 0;
+        uint64_t nextmask = 0, guessmask = 0;                                  // guessmask: stored only because the peek was unknown (no record at hand copies from them)
         {
             uint32_t tgt = 64;                                                // lane of this super-row that my peeked node references
             bool unknown = false;
@@ -646,8 +662,8 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
                     }
                 }
             }
-            if (ballot(unknown)) nextmask |= K1 >= W ? (~0ull << (K1 - W)) : ~0ull;
-            for (uint32_t j = 0; j < W && j < 64; j++) { const uint32_t t = lane_get(tgt, j); if (t < 64) nextmask |= 1ull << t; }
+            if (ballot(unknown)) { nextmask |= K1 >= W ? (~0ull << (K1 - W)) : ~0ull; guessmask = nextmask & ~refmask; }
+            for (uint32_t j = 0; j < W && j < 64; j++) { const uint32_t t = lane_get(tgt, j); if (t < 64) { nextmask |= 1ull << t; guessmask &= ~(1ull << t); } }
             refmask |= nextmask;
         }
         BVG_T1(15, tqp);
@@ -700,6 +716,28 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
             sk_run += lane_get(eincl, 63);
         }
         if (sk_run > sk_n) { failed = true; fail_need = kFailCode; break; }     // index out of step with the stream
+        // ... and its recorded positions, likewise: a node has entries when some later node of the GRAPH copies from it (`copied_from` says "may", and knows this
+        // block only) -- a function of the stream alone, whatever the pool, the window and the scratch area make of the rows
+        const bool hasent = posm && parse && ((refw >> ((uint32_t)x & 31u)) & 1u) != 0 && d < 0xFFFFu;
+        uint32_t pfirst = 0;
+        // the node's entries are on file.  One scan writes a node's entries all or not at all (it fails only between sub-rows, and then sets no flag).  NOT closed: two handles
+        // in different geometries recording the same block at once -- one, in which the node is stored on a guess, half-way through its entries while the other, in which
+        // it is a leaf, releases the flag; a reader would then find the first entry written and later ones 0xFFFF, which the guard below drops.
+        bool pwritten = false;
+        if (posm) {
+            const uint32_t pcnt = hasent ? (ref > 0 ? nres + ic : ic) : 0u;
+            const uint32_t pincl = wave_incl_scan32(pcnt);
+            pfirst = ps_run + pincl - pcnt;
+            ps_run += lane_get(pincl, 63);
+            if (ps_run > ps_n) { failed = true; fail_need = kFailCode; break; }   // (out of step: no entry beyond the block's own is ever touched)
+            // An entry nobody has written reads 0xFFFF, which no position is (d < 0xFFFF).  The flag says that every list the RECORDING scan stored has its entries; a
+            // list that was a leaf there (copied from the next block only) and is stored here (another geometry: a peek unknown, a super-row cut short) has none
+            // and keeps Z1 (entries are written only in front of the flag's release, never behind it).
+            // Whoever a record of this block is seen to copy from was stored by the recording scan too, whatever its geometry: only a list stored on a guess can be
+            // without entries, so only those lanes look (none at all in most super-rows).
+            pwritten = pos_use;
+            if (pos_use && ((guessmask >> lane) & 1ull) && pcnt != 0u) pwritten = a.pos_ent[ps_base + pfirst] != 0xFFFFu;
+        }
         BVG_T1(8, tq8);
         BVG_T1(5, tq5);
 
@@ -951,6 +989,41 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
             uint64_t remaining = ballot(emits);                               // (a sub-row whose stored lists were all decoded in place runs no level)
             wave_sync();
             BVG_T1(0, tq0);
+            // ---------------- the extras of EVERY level's members at once, from their recorded positions: nothing here looks at a referenced list, so no member has
+            // to wait for its level.  A lane per extra, dealt as in Z1; the entries of a node are consecutive (its intervals, then its residuals) and those of a
+            // sub-row nearly so.  What is stored is what Z1 stores: a residual goes to its place and leaves its position where it was parked, an interval's entry
+            // gets its position.  A member without entries (stored only because a peek was unknown or the super-row was cut short), or whose entries nobody has
+            // written yet, keeps Z1, in its own level.
+            const bool posl = pos_use && emits && hasent && pwritten;
+            if (pos_use) {
+                const uint32_t tq3 = BVG_T0();
+                const uint32_t In = posl ? nresN + ic : 0u;
+                const uint32_t iincl2 = wave_incl_scan32(In), is = iincl2 - In, Itot = lane_get(iincl2, 63);
+                for (uint32_t p0 = 0; p0 < Itot; p0 += 64) {
+                    const bool tl = p0 + lane < Itot;
+                    BVG_WC(3, 1);
+                    const uint32_t own = deal_few(ballot(In != 0), iincl2, is, p0 + lane);
+                    const int nl = tl ? (int)own : (int)lane;
+                    const uint32_t s_first = (uint32_t)__shfl((int)is, nl, 64);
+                    const uint32_t q = tl ? p0 + lane - s_first : 0u;
+                    const uint32_t t_d = __shfl(d, nl, 64), t_ic = __shfl(ic, nl, 64), t_ib = __shfl(ib, nl, 64);
+                    const uint32_t t_rtb = __shfl(rtbN, nl, 64), t_ob = __shfl(base, nl, 64), t_pf = __shfl(pfirst, nl, 64);
+                    T* const rt = pool + t_rtb;
+                    T vv = 0; uint32_t len = 0, pe = 0; const bool isiv = q < t_ic;
+                    if (tl) {
+                        pe = a.pos_ent[ps_base + t_pf + q];
+                        if (isiv) len = (uint32_t)(scr[t_ib + 2 * q + 1] & HM); else { vv = rt[q - t_ic]; len = 1; }
+                        if (pe + len > t_d) { pe = 0; len = 0; }              // (cannot happen in a validated block; never write outside the list)
+                    }
+                    wave_sync();
+                    if (tl && len) {
+                        if (isiv) scr[t_ib + 2 * q + 1] = (T)len | (T)((T)pe << HS);
+                        else { pool[t_ob + pe] = vv; rt[q - t_ic] = (T)pe; }
+                    }
+                    wave_sync();
+                }
+                BVG_T1(3, tq3);
+            }
             // WW: which of the lists with reference are built wave-wide
             const bool wwn = wwon && emits && ref > 0 && d <= kWWBits && rlenS <= kWWBits && d >= (a.dbg >> 16);   // (bits 16.. of BVG_DBG: the shortest list built this way)
             bool wwbad = false;
@@ -974,7 +1047,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
                 // ---------------- Z1: one lane per extra: its output position = (extras below it) + (copied elements below it)
                 const uint32_t tq3 = BVG_T0();
                 {
-                    const uint32_t In = mem ? nresN + ic : 0u;
+                    const uint32_t In = (mem && !posl) ? nresN + ic : 0u;     // (members whose extras were placed from their recorded positions are done)
                     uint64_t fsum = 0;                                        // (ZE only)
                     const uint32_t iincl2 = wave_incl_scan32(In), is = iincl2 - In, Itot = lane_get(iincl2, 63);
 #ifdef BVG_ABLATE_Z1
@@ -991,6 +1064,8 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
                         const uint32_t t_bc = __shfl(bc, nl, 64), t_sb = __shfl(sb, nl, 64), t_ic = __shfl(ic, nl, 64), t_ib = __shfl(ib, nl, 64);
                         const uint32_t t_nres = __shfl(nresN, nl, 64), t_rtb = __shfl(rtbN, nl, 64), t_ob = __shfl(base, nl, 64);
                         const T* const rl = pool + t_rlb; T* const rt = pool + t_rtb;
+                        uint32_t t_pf = kInf;                                 // recording: the node's first entry (kInf: it has none)
+                        if (pos_rec) t_pf = __shfl(hasent ? pfirst : kInf, nl, 64);   // (wave-uniform: the shuffle is executed by every lane; entries are written in front of the flag's release only)
                         bool t_gl = false; int64_t* gp = nullptr;             // MAT: the task's list is a leaf merged straight into the output
                         if (MAT) {
                             const uint32_t s_gl = (uint32_t)__shfl((int)(gl ? 1 : 0), nl, 64), g_lo = __shfl((uint32_t)gofs, nl, 64), g_hi = __shfl((uint32_t)(gofs >> 32), nl, 64);
@@ -1025,6 +1100,7 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
                             if (pe + len > t_d) { pe = 0; len = 0; }          // (cannot happen in a validated block; never write outside the list)
                         }
                         wave_sync();                                      // the parked values have been read: positions may replace them
+                        if (tl && len && t_pf != kInf) a.pos_ent[ps_base + t_pf + q] = (uint16_t)pe;   // (idempotent: every scan of the block finds the same position)
                         if (tl && len) {
                             if (isiv && zel) {                                // ZE: the interval is written here, element by element (LongIntervalSequenceIterator.java:71-78), and its places are marked
                                 for (uint32_t i = 0; i < len; i++) { pool[t_ob + pe + i] = (T)(vv + i); fsum += mix_node<T>(z_k1, (T)(vv + i)); atomicOr(&zem[t_eb + ((pe + i) >> 5)], 1u << ((pe + i) & 31u)); }
@@ -1441,6 +1517,11 @@ __global__ void __launch_bounds__(64, OCC) scan_kernel(DecodeArgs a) {
         return;
     }
     blk_arcs = wave_sum64(blk_arcs); blk_chk = wave_sum64(blk_chk); blk_nodes = wave_sum64(blk_nodes);
+    if (pos_rec) {                                                            // every entry of the block is written: publish them (every lane's stores first)
+        __threadfence();
+        if (lane == 0) __hip_atomic_store(&a.pos_ready[bid], (uint8_t)kPosNeed, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (posm && a.pos_stat && lane == 0) atomicAdd(&a.acc[2 * kAccStride + (pos_use ? 4 : 5)], 1ull);
     if (lane == 0) {
         unsigned long long* const accs = a.acc + (size_t)(bid & a.acc_mask) * kAccStride;   // this block's result stripe
         atomicAdd(&accs[0], (unsigned long long)blk_arcs);

@@ -203,6 +203,10 @@ static int base_args(Decode& d, const uint64_t* d_cum, int64_t* d_succ, int32_t*
     a.xcds = d.k.xcds; a.wide_half = d.k.wide_half;
     if (!batch && d.rows_default && d.skx && d.skx->wide == d.wide) {
         a.skip_first = d.skx->d_first; a.skip_bit = d.skx->d_bit; a.skip_val = d.skx->d_val; a.skip_fmt = d.skx->d_fmt;
+        // the recorded positions of the snapshot (scan mode of the lean scan kernel only); a marks-only handle has no entries at all, BVG_NO_POS=1 keeps the searches
+        if (!d.materialise && g->skip_mode == 0 && !d.skx->h_pos_first.empty() && g->tun.no_index != 2 && !(knob("BVG_NO_POS") && atoi(knob("BVG_NO_POS")))) {
+            a.pos_refd = d.skx->pos_refd; a.pos_first = d.skx->pos_first; a.pos_ent = d.skx->pos_ent; a.pos_ready = d.skx->pos_ready; a.pos_stat = dbg_on() ? 1u : 0u;
+        }
     }
     a.grab_threshold = (g->tun.reserved >> 8) ? (g->tun.reserved >> 8) : 40;
     // tier 2a (bvg_giant.hip): lists / records too large for LDS, decoded by a whole workgroup each; default codings and windows <= 64
@@ -481,8 +485,13 @@ static int launch_concurrent(Decode& d, const GiantWs& gw) {
     float ms = 0; HIPCHK(hipEventElapsedTime(&ms, g->ev0, g->ev1));
     d.kernel_ms += ms;
     const uint32_t* n = pd.count;
-    if (dbg_on()) fprintf(stderr, "[bvg] tiers concurrent: scan kernel %u + %u/%u/%u/%u LDS-class, row kernel %u + %u/%u/%u/%u LDS-class, %u giant + %u generic blocks, %.3f ms\n",
-                          n[Pred::kLean0], n[Pred::kLeanC1], n[Pred::kLeanC2], n[Pred::kLeanC3], n[Pred::kLeanC4], n[Pred::kRow0], n[Pred::kRowC1], n[Pred::kRowC2], n[Pred::kRowC3], n[Pred::kRowC4], n[Pred::kGiant], n[Pred::kGeneric], ms);
+    if (dbg_on()) {
+        unsigned long long ps[2] = {0, 0};                  // scan-kernel blocks that read their extras' positions back / that searched for them and wrote them down (a debug
+                                                            // figure: fetched with a synchronous copy, and printed for the concurrent launch of the tiers only -- the cascade's launches print none)
+        if (d.af.pos_stat) HIPCHK(hipMemcpy(ps, g->d_acc + 2 * kAccStride + 4, sizeof ps, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[bvg] tiers concurrent: scan kernel %u + %u/%u/%u/%u LDS-class, row kernel %u + %u/%u/%u/%u LDS-class, %u giant + %u generic blocks, %.3f ms; positions: %llu blocks recorded, %llu recording\n",
+                n[Pred::kLean0], n[Pred::kLeanC1], n[Pred::kLeanC2], n[Pred::kLeanC3], n[Pred::kLeanC4], n[Pred::kRow0], n[Pred::kRowC1], n[Pred::kRowC2], n[Pred::kRowC3], n[Pred::kRowC4], n[Pred::kGiant], n[Pred::kGeneric], ms, ps[0], ps[1]);
+    }
     return 0;
 }
 
@@ -647,6 +656,8 @@ static int finish(Decode& d) {
         res->index_bytes = (uint64_t)(to - from + 1) * (d.sh->offs.lo ? 4 : 8) + (d.sh->offs.lo ? ((uint64_t)(to - from) >> kOffShift) * 8 : 0) + (uint64_t)nblocks * 20;
         res->index_entries = a.skip_first && d.skx->h_first.size() > (size_t)lo + nblocks ? d.skx->h_first[lo + nblocks] - d.skx->h_first[lo] : 0;
         if (a.skip_first) res->index_bytes += res->index_entries * (2 + d.esz) + (uint64_t)nblocks * 9;
+        if (a.pos_first && d.skx->h_pos_first.size() > (size_t)lo + nblocks)       // recorded positions: the entries, a base and a flag per block, a bit per node
+            res->index_bytes += (d.skx->h_pos_first[lo + nblocks] - d.skx->h_pos_first[lo]) * 2 + (uint64_t)nblocks * 9 + ((uint64_t)(to - from) >> 3);
         res->graph_bytes = 0;
     }
     if (acc[3] && dbg_on()) fprintf(stderr, "[bvg] error bits 0x%llx\n", acc[3]);
