@@ -662,6 +662,31 @@ int  bvg_transform_union(const bvg_transform_src* a, const bvg_transform_src* b,
 int  bvg_transform_permutation(const bvg_transform_src* src, int kind, uint64_t seed, int64_t* perm);
 int  bvg_transform_permutation_dev(const bvg_transform_src* src, int kind, uint64_t seed, void* d_perm);
 
+/* ---- Compose (Transform.compose, T:1666-1775, the unlabelled form): the product of two graphs, every row hashed on chip ----
+ * The result has n = max(nodes0, nodes1) nodes.  Row x is the sorted set of the successors in g1 of the successors of x in g0: the union of
+ * N1(y) over y in N0(x) with y < nodes1.  Rows x >= nodes0 are empty.  A successor y >= nodes1 contributes nothing: the reference would
+ * throw when its iterator reaches such a node; here a node a graph does not have is a node without successors, as in the padding of
+ * bvg_transform_union.  The sources are those of Transform above (a bvg_graph is decoded once and checked, node base 0: else BVG_E_ARG;
+ * both or neither member set, or a NULL source: BVG_E_ARG); when g0 and g1 name the same handle it is resolved once.  The result is the
+ * bvg_text of the transforms and can be the source of the next call.
+ * LIMITS: a source or a result of 2^31 arcs or more, or 2^31 nodes or more: BVG_E_UNSUPPORTED.  A row holds at most nodes1 < 2^31
+ * successors, so no single row's count can wrap.  The number of products (pairs of an arc x -> y of g0 and an arc y -> z of g1) has no
+ * limit: no stage stores them.  Sources on different devices: BVG_E_ARG.  *out is written on success only.  `report` (may be NULL) is filled
+ * on success, and also when the result is refused for its size: products, rows, limit, and arcs = the total that was refused.
+ * DEVICE MEMORY, besides sources and result: 16 bytes per node (the rows' bounds, 8; their lengths, 4; the tier lists, 4; the scan's
+ * temporaries) plus 8 bytes per row of tier 2, and tier 2's workspace: hash tables of 16 pow2ceil(min(bound, nodes)) bytes per row, as many
+ * rows side by side as fit 256 MiB (a row whose table alone is larger gets a workspace of that size); the host holds 12 bytes per node
+ * during the call.  BVG_E_NOMEM leaves nothing allocated.  A probe sequence that does not end within its table (it cannot: a table is at
+ * most half full) is BVG_E_HIP, never a spin. */
+typedef struct bvg_compose_report {   /* 64 bytes */
+    uint64_t products;     /* sum of the rows' bounds: arcs (x, y) of g0 times outdeg1(y) */
+    uint64_t arcs;         /* of the result */
+    uint64_t rows[3];      /* rows with a bound > 0 that tier 0 (a wavefront, LDS) / 1 (a workgroup, LDS) / 2 (a workgroup, HBM) took */
+    uint64_t limit[2];     /* the largest bound a row of tier 0 / tier 1 may have, in this build */
+    uint64_t batches;      /* launches of tier 2's batches per pass; 0 when no row needed it */
+} bvg_compose_report;
+int  bvg_compose(const bvg_transform_src* g0, const bvg_transform_src* g1, bvg_compose_report* report, bvg_text** out);
+
 /* ---- synthetic-workload helper (bench only): K back-to-back copies of the graph ----
  * BV records are translation invariant (every value is coded relative to the node id, Appendix A.3
  * of SURVEY.md), so the concatenation of K copies of the bit stream is a valid BVGraph with K*nodes

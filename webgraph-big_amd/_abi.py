@@ -177,6 +177,20 @@ def transform_signatures():
             "bvg_transform_permutation": [S, ci, u64, vp], "bvg_transform_permutation_dev": [S, ci, u64, vp]}
 
 
+class ComposeReport(C.Structure):
+    """bvg_compose_report (64 bytes): what bvg_compose did with the rows."""
+    _fields_ = [("products", C.c_uint64), ("arcs", C.c_uint64), ("rows", C.c_uint64 * 3), ("limit", C.c_uint64 * 2), ("batches", C.c_uint64)]
+
+    def as_dict(self):
+        return {"products": int(self.products), "arcs": int(self.arcs), "rows": [int(v) for v in self.rows], "limit": [int(v) for v in self.limit], "batches": int(self.batches)}
+
+
+def compose_signatures():
+    """argtypes of bvg_compose, by name (a function of its own: transform_signatures() is the set of the bvg_transform_* names)."""
+    S = C.POINTER(TransformSrc)
+    return {"bvg_compose": [S, S, C.POINTER(ComposeReport), C.POINTER(C.c_void_p)]}
+
+
 OK, E_ARG, E_STATE, E_UNSUPPORTED, E_IO, E_EOF, E_NOMEM, E_HIP, E_CAPACITY = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 

@@ -376,6 +376,19 @@ int batch_decode(bvg_graph* g, const BatchBufs& b, int64_t count, int64_t* d_suc
 // `nodes` is dropped).  s0 / d0 are used up.  Fewer than 2^31 pairs (BVG_E_UNSUPPORTED beyond), at most 2^40 nodes (BVG_E_NOMEM).
 int pairs_to_csr(DevArray<uint64_t>& s0, DevArray<uint64_t>& d0, uint64_t np, int64_t nodes, bvg_text* t);
 
+// ---- bvg_transform.hip: the sources of the graph-to-graph calls (bvg_transform_*, bvg_compose).  A bvg_text is used where it lies; a bvg_graph is
+// decoded once into a CSR of its own (`own`) and checked as bvg_store checks its input; a node base other than 0 is BVG_E_ARG.
+struct Source {
+    int device = 0; int64_t n = 0; uint64_t m = 0; const uint64_t* off = nullptr; const int64_t* adj = nullptr;
+    std::unique_ptr<bvg_text> own;          // a decoded bvg_graph
+};
+bool one_source(const bvg_transform_src* s);                                        // exactly one of the two handles is set
+int source_device(const bvg_transform_src* s);
+int resolve(const bvg_transform_src* s, Source& r);
+std::unique_ptr<bvg_text> new_csr(int device);
+int check_csr(const uint64_t* d_off, const int64_t* d_adj, int64_t n, int refused);   // 0, or `refused` when the CSR is not one bvg_store would take
+int finish(std::unique_ptr<bvg_text>& t, bvg_text** out);                            // the device drained, then *out
+
 // ---- bvg_index_host.hip
 void skip_granularity(const Shared* sh, uint32_t& smin, uint32_t& shift);
 int build_skip(bvg_graph* g, const std::shared_ptr<Plan>& plp, uint32_t blo, uint32_t bhi, bool retry_failed = false, bvg_scan_result* first_scan = nullptr, int64_t sfrom = 0, int64_t sto = 0, bool* first_scan_done = nullptr);

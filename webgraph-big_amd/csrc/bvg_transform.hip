@@ -151,14 +151,11 @@ __global__ void perm_invert_kernel(const uint32_t* node, int64_t n, int64_t* per
     BVG_FOR(r, n) perm[node[r]] = r;
 }
 
-// ---- sources
-struct Source {
-    int device = 0; int64_t n = 0; uint64_t m = 0; const uint64_t* off = nullptr; const int64_t* adj = nullptr;
-    std::unique_ptr<bvg_text> own;          // a decoded bvg_graph
-};
+}  // namespace
 
+// ---- sources (Source, and the functions outside the unnamed namespaces here, are declared in bvg_host.h: bvg_compose.hip uses them too)
 bool one_source(const bvg_transform_src* s) { return s && (s->graph != nullptr) != (s->csr != nullptr); }
-int64_t source_nodes(const bvg_transform_src* s) { return s->csr ? s->csr->nodes : s->graph->sh->p.nodes; }
+int source_device(const bvg_transform_src* s) { return s->csr ? s->csr->device : s->graph->sh->device; }
 
 std::unique_ptr<bvg_text> new_csr(int device) { std::unique_ptr<bvg_text> t(new bvg_text); t->device = device; return t; }
 
@@ -172,6 +169,10 @@ int check_csr(const uint64_t* d_off, const int64_t* d_adj, int64_t n, int refuse
     HIPCHK(hipMemcpy(&hb, bad.get(), sizeof hb, hipMemcpyDeviceToHost));
     return hb ? refused : 0;
 }
+
+namespace {
+
+int64_t source_nodes(const bvg_transform_src* s) { return s->csr ? s->csr->nodes : s->graph->sh->p.nodes; }
 
 int decode_graph(bvg_graph* g, std::unique_ptr<bvg_text>& out) {
     if (g->node_base != 0) return BVG_E_ARG;                 // a shard's targets leave its node range
@@ -201,6 +202,8 @@ int decode_graph(bvg_graph* g, std::unique_ptr<bvg_text>& out) {
     return 0;
 }
 
+}  // namespace
+
 int resolve(const bvg_transform_src* s, Source& r) {
     if (s->graph) {
         const int rc = decode_graph(s->graph, r.own); if (rc) return rc;
@@ -213,18 +216,20 @@ int resolve(const bvg_transform_src* s, Source& r) {
     return 0;
 }
 
+int finish(std::unique_ptr<bvg_text>& t, bvg_text** out) {
+    HIPCHK(hipDeviceSynchronize());
+    *out = t.release();
+    return 0;
+}
+
+namespace {
+
 // a caller's array of `count` int64 on the device: the array itself (_dev), or a copy
 int on_device_i64(const void* p, int64_t count, bool dev, DevArray<int64_t>& hold, const int64_t** out) {
     if (dev) { *out = (const int64_t*)p; return 0; }
     if (hold.alloc((size_t)count)) return BVG_E_NOMEM;
     if (count) HIPCHK(hipMemcpy(hold.get(), p, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice));
     *out = hold.get();
-    return 0;
-}
-
-int finish(std::unique_ptr<bvg_text>& t, bvg_text** out) {
-    HIPCHK(hipDeviceSynchronize());
-    *out = t.release();
     return 0;
 }
 
@@ -503,7 +508,7 @@ int bvg_transform_symmetrize(const bvg_transform_src* src, uint32_t flags, bvg_t
 
 int bvg_transform_union(const bvg_transform_src* a, const bvg_transform_src* b, uint32_t flags, bvg_text** out) {
     if (!out || !one_source(a) || !one_source(b) || (flags & ~(uint32_t)BVG_TRANSFORM_DROP_LOOPS)) return BVG_E_ARG;
-    if ((a->csr ? a->csr->device : a->graph->sh->device) != (b->csr ? b->csr->device : b->graph->sh->device)) return BVG_E_ARG;
+    if (source_device(a) != source_device(b)) return BVG_E_ARG;
     return with_source(a, [&](const Source& sa) -> int {
         Source sb;
         int rc = resolve(b, sb); if (rc) return rc;

@@ -649,6 +649,14 @@ template <class A, class B> std::unique_ptr<ParsedGraph> unionGraphs(A& a, B& b,
     const int st = bvg_transform_union(&sa, &sb, dropLoops ? BVG_TRANSFORM_DROP_LOOPS : 0u, &t);
     return finishTransform(st, t, "unionGraphs");
 }
+// Transform.compose (unlabelled): row x = the sorted union of b's lists over a's successors of x; max(nodes) nodes, a successor b does not
+// have contributes nothing.  report: products, arcs, the rows each tier took (bvg_compose_report)
+typedef bvg_compose_report ComposeReport;
+template <class A, class B> std::unique_ptr<ParsedGraph> composeGraphs(A& a, B& b, ComposeReport* report = nullptr) {
+    bvg_text* t = nullptr; const bvg_transform_src sa = transformSource(a), sb = transformSource(b);
+    const int st = bvg_compose(&sa, &sb, report, &t);
+    return finishTransform(st, t, "composeGraphs");
+}
 // perm[node] = the node's new name (kind = BVG_PERM_LEX / BVG_PERM_GRAY / BVG_PERM_RANDOM), ready for mapGraph
 template <class G> std::vector<int64_t> permutation(G& g, int kind, uint64_t seed = 0) {
     std::vector<int64_t> perm((size_t)g.numNodes());

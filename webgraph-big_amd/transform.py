@@ -1,6 +1,7 @@
 """Transform over the C ABI (include/bvgraph_hip.h, bvg_transform_*): map, filter, transpose, symmetrise, simplify, union and the
 lexicographic / Gray code / random permutations, every result a ParsedGraph (a CSR resident on the device) that can be the source of
-the next call, be stored or be written as text; BinIO / TextIO longs; and the command line of Transform.main (Transform.java:2070-2381)."""
+the next call, be stored or be written as text; the unlabelled composition (bvg_compose) with its own command line; BinIO / TextIO longs; and
+the command line of Transform.main (Transform.java:2070-2381)."""
 import ctypes as C
 import sys
 
@@ -124,6 +125,35 @@ def union(a, b, drop_loops=False):
         h = C.c_void_p()
         _check(_transform_fns().bvg_transform_union(C.byref(sa.src), C.byref(sb.src), _abi.TRANSFORM_DROP_LOOPS_FLAG if drop_loops else 0, C.byref(h)), "union")
         return ParsedGraph(h, sa.device)
+
+
+def _compose_fns():
+    """bvg_compose, bound on first use."""
+    L = lib()
+    if getattr(L, "_compose_bound", False):
+        return L
+    for name, args in _abi.compose_signatures().items():
+        if not hasattr(L, name):
+            raise UnsupportedOperationException(_abi.E_UNSUPPORTED, name + " is not in this build of the library")
+        getattr(L, name).argtypes = args
+    L._compose_bound = True
+    return L
+
+
+def compose(a, b, report=False):
+    """Transform.compose(a, b), unlabelled: row x of the result is the sorted union of b's lists over a's successors of x; max(nodes) nodes; a
+    successor that b does not have contributes nothing.  report=True: (graph, dict of bvg_compose_report).  A result refused for its size
+    raises UnsupportedOperationException carrying the report as .report."""
+    with _Source(a) as sa, _Source(b) as sb:
+        h, rep = C.c_void_p(), _abi.ComposeReport()
+        st = _compose_fns().bvg_compose(C.byref(sa.src), C.byref(sb.src), C.byref(rep), C.byref(h))
+        try:
+            _check(st, "compose")
+        except UnsupportedOperationException as e:
+            e.report = rep.as_dict()
+            raise
+        g = ParsedGraph(h, sa.device)
+        return (g, rep.as_dict()) if report else g
 
 
 def _permutation(g, kind, seed=0):
@@ -294,6 +324,44 @@ def transform_main(argv=None):
             perm = gray_code_permutation(g) if t == "gray" else lexicographical_permutation(g) if t == "lex" else random_permutation(g, seed)
             result = map_graph(g, perm)
         _store_result(dcls, result, dest, a.device)
+    finally:
+        if result is not None:
+            result.close()
+        for s in sources:
+            s.close()
+    return 0
+
+
+def compose_arg_parser():
+    import argparse
+    ap = argparse.ArgumentParser(prog="compose_main", description="Composes two graphs on the device (Transform.main's compose, unlabelled): "
+                                 "source0 source1 dest.")
+    ap.add_argument("-s", "--source-graph-class", dest="source_graph_class", default="BVGraph")
+    ap.add_argument("-d", "--dest-graph-class", dest="dest_graph_class", default="BVGraph")
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("param", nargs="*")
+    return ap
+
+
+def compose_main(argv=None):
+    """Transform.main's `compose`: [-s CLASS] [-d CLASS] [--device N] source0 source1 dest.  Returns 0, or 1 after a message for a wrong
+    number of parameters and for the fourth one (the semiring of the labelled composition, which is not built).  It is a command of its own
+    because transform_main's answer to `compose` -- 1, before anything is opened -- is pinned by tests/test_transform_abi.py."""
+    a = compose_arg_parser().parse_args(argv)
+    p = a.param
+    if len(p) == 4:
+        print("compose_main: labelled graphs are not built", file=sys.stderr)
+        return 1
+    if len(p) != 3:
+        print("compose_main: I need 3 arguments rather than %d." % len(p), file=sys.stderr)
+        return 1
+    scls, dcls = _class_name(a.source_graph_class), _class_name(a.dest_graph_class)
+    sources, result = [], None
+    try:
+        for name in p[:2]:
+            sources.append(_open_source(scls, name, a.device))
+        result = compose(sources[0], sources[1])
+        _store_result(dcls, result, p[2], a.device)
     finally:
         if result is not None:
             result.close()
