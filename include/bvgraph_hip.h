@@ -687,6 +687,65 @@ typedef struct bvg_compose_report {   /* 64 bytes */
 } bvg_compose_report;
 int  bvg_compose(const bvg_transform_src* g0, const bvg_transform_src* g1, bvg_compose_report* report, bvg_text** out);
 
+/* ---- Arc-labelled graphs on the device: Transform's labelled half and BitStreamArcLabelledImmutableGraph.store ("BS") ----
+ * A bvg_lgraph is a graph as the transforms above hold it (a CSR in HBM) plus int32 labels[arcs] in successor order and the label class:
+ * kind BVG_LABEL_GAMMA_INT (GammaCodedIntLabel: every label >= 0) or BVG_LABEL_FIXED_INT (FixedWidthIntLabel: width in 0..31,
+ * FixedWidthIntLabel.java:41-42, every label in [0, 2^width)).  Every graph-valued call goes from bvg_lgraph to bvg_lgraph and keeps the class, so
+ * a result can be the source of the next call, be read back, or be written as a label stream without leaving the device.  The list label
+ * classes are BVG_E_UNSUPPORTED everywhere here.  *out is written on success only; NULL handles, unknown kinds and strategies: BVG_E_ARG,
+ * decided before any handle is looked at.
+ *   bvg_lgraph_from_csr[_dev]  a handle over a copy of the caller's CSR and labels.  The CSR is validated exactly as bvg_transform_from_csr
+ *                        validates it (the same kernel, the same refusals); the labels are validated on the device: a negative gamma label, a
+ *                        fixed label outside [0, 2^width) or a width outside 0..31 is BVG_E_ARG, a list kind BVG_E_UNSUPPORTED.
+ *   bvg_lgraph_from_labelled   an open BVGraph and its label stream: the graph is decoded once and checked as a bvg_transform_src is, the labels
+ *                        through bvg_labels_decode_range_dev (its errors are handed on unchanged).  Different devices, different node counts or
+ *                        a node base other than 0: BVG_E_ARG; list labels, and a FixedWidthIntLabel of 32 bits: BVG_E_UNSUPPORTED.
+ *   bvg_lgraph_info / _get / _get_dev   sizes and class; adj_off[nodes + 1], adj[arcs], labels[arcs] under the capacity contract of bvg_text_get
+ *                        (any of the three may be NULL; a capacity in elements below the size: BVG_E_CAPACITY, nothing written).
+ *   bvg_lgraph_underlying   the unlabelled graph as a bvg_text of its own (a copy): every bvg_transform_* call, bvg_compose and bvg_text_store
+ *                        apply to it.
+ *   bvg_lgraph_transpose T.transposeOffline(ArcLabelledImmutableGraph...) (T:1337-1631): arc (x, y) with label l becomes (y, x) with label l, lists
+ *                        sorted by successor.  (target, source) is unique, so nothing about the result is left open.
+ *   bvg_lgraph_union     T.union / UnionArcLabelledImmutableGraph: max(nodes_a, nodes_b) nodes; an arc of one source keeps its label, an arc of
+ *                        both gets merge(label_a, label_b), a's label first (UnionArcLabelledImmutableGraph.java:188).  Strategies:
+ *                        BVG_LMERGE_KEEP_FIRST (Labels.KEEP_FIRST_MERGE_STRATEGY, the only one the reference ships), BVG_LMERGE_MIN, BVG_LMERGE_MAX.
+ *                        All three pick one of their arguments, so the result is storable in the sources' class.  A LabelMergeStrategy written
+ *                        by the user is Java code and cannot run on the device: there is no entry point for one.  Sources whose (kind, width)
+ *                        differ or that live on different devices: BVG_E_ARG.
+ *   bvg_lgraph_symmetrize   union(g, transpose(g), strategy), as T:633-635 has it.
+ *   bvg_lgraph_filter    T.filterArcs with a LabelledArcFilter.  BVG_LFILTER_NO_LOOPS / _SAME_CLASS / _DIFFERENT_CLASS are the filters of
+ *                        bvg_transform_filter under the same numbers and rules (node_class NULL and class_len 0 without classes; class_len =
+ *                        nodes with them); BVG_LFILTER_LOWER_BOUND is T.LowerBound AS THE CODE HAS IT (T:213): an arc stays iff
+ *                        label >= lower_bound (the javadoc says "larger").  lower_bound must be 0 with every other kind, node_class NULL with
+ *                        LOWER_BOUND: BVG_E_ARG.  The node count is unchanged.
+ *   bvg_lgraph_store_labels   BS.store (BS:654-684): the bytes of basename.labels -- per arc gamma(label) (2 msb(label + 1) + 1 bits, up to 63) or
+ *                        `width` bits, MSB first, zero-padded to a byte -- and label_offsets[nodes + 1], the bit position of every node's first
+ *                        label (write basename.labeloffsets from their gamma-coded gaps after a leading gamma(0)).  Width 0: an empty stream and
+ *                        offsets all zero.  Both buffers are malloc'ed (bvg_free), as bvg_text_store returns its buffers.  _dev: the caller's
+ *                        device buffers, d_stream of `cap` bytes and d_label_offsets of nodes + 1 uint64 (either may be NULL); *nbytes is always
+ *                        filled, cap below it is BVG_E_CAPACITY and nothing is written.
+ * LIMITS: a source or a result of 2^31 arcs or more: BVG_E_UNSUPPORTED.  DEVICE MEMORY, besides sources and result: transpose 16 bytes per arc
+ * plus the sort's workspace; union 4 bytes per arc of a and 16 per arc of b; symmetrize both, and the transpose itself; filter 12 per arc;
+ * store_labels 12 per arc, 8 per node and the stream.  BVG_E_NOMEM leaves nothing allocated.
+ * Not built: compose with a LabelSemiring, list labels through the transforms, user-written strategies and filters, several devices. */
+typedef struct bvg_lgraph bvg_lgraph;
+enum { BVG_LMERGE_KEEP_FIRST = 0, BVG_LMERGE_MIN = 1, BVG_LMERGE_MAX = 2 };
+enum { BVG_LFILTER_NO_LOOPS = 0, BVG_LFILTER_SAME_CLASS = 1, BVG_LFILTER_DIFFERENT_CLASS = 2, BVG_LFILTER_LOWER_BOUND = 3 };
+int  bvg_lgraph_from_csr(int64_t nodes, const uint64_t* adj_off, const int64_t* adj, const int32_t* labels, int kind, int width, int device, bvg_lgraph** out);
+int  bvg_lgraph_from_csr_dev(int64_t nodes, const void* d_adj_off, const void* d_adj, const void* d_labels, int kind, int width, int device, bvg_lgraph** out);
+int  bvg_lgraph_from_labelled(bvg_graph* g, bvg_labels* labels, bvg_lgraph** out);
+void bvg_lgraph_close(bvg_lgraph* l);
+int  bvg_lgraph_info(const bvg_lgraph* l, int64_t* nodes, uint64_t* arcs, int* kind, int* width);
+int  bvg_lgraph_get(bvg_lgraph* l, uint64_t* adj_off, uint64_t off_cap, int64_t* adj, uint64_t adj_cap, int32_t* labels, uint64_t labels_cap);
+int  bvg_lgraph_get_dev(bvg_lgraph* l, void* d_adj_off, uint64_t off_cap, void* d_adj, uint64_t adj_cap, void* d_labels, uint64_t labels_cap);
+int  bvg_lgraph_underlying(const bvg_lgraph* l, bvg_text** out);
+int  bvg_lgraph_transpose(const bvg_lgraph* src, bvg_lgraph** out);
+int  bvg_lgraph_union(const bvg_lgraph* a, const bvg_lgraph* b, int strategy, bvg_lgraph** out);
+int  bvg_lgraph_symmetrize(const bvg_lgraph* src, int strategy, bvg_lgraph** out);
+int  bvg_lgraph_filter(const bvg_lgraph* src, int kind, const int64_t* node_class, int64_t class_len, int64_t lower_bound, bvg_lgraph** out);
+int  bvg_lgraph_store_labels(const bvg_lgraph* l, uint8_t** stream, uint64_t* nbytes, uint64_t** label_offsets);
+int  bvg_lgraph_store_labels_dev(const bvg_lgraph* l, void* d_stream, uint64_t cap, uint64_t* nbytes, void* d_label_offsets);
+
 /* ---- synthetic-workload helper (bench only): K back-to-back copies of the graph ----
  * BV records are translation invariant (every value is coded relative to the node id, Appendix A.3
  * of SURVEY.md), so the concatenation of K copies of the bit stream is a valid BVGraph with K*nodes

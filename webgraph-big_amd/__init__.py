@@ -25,3 +25,6 @@ from .textgraph import (ParsedGraph, parse_ascii_graph, parse_arc_list, parse_as
 from . import transform  # noqa: F401,E402
 from .transform import (identity_graph, map_graph, filter_arcs, transpose_graph, symmetrize_graph, simplify_graph, union, remove_dangling,  # noqa: F401,E402
                         lexicographical_permutation, gray_code_permutation, random_permutation, permutation_dev, load_longs, store_longs, transform_main, compose, compose_main)
+from . import labelled  # noqa: F401,E402
+from .labelled import (LabelledGraph, transpose_labelled, union_labelled, symmetrize_labelled, filter_labelled_arcs, label_spec,  # noqa: F401,E402
+                       labelled_transform_main)

@@ -191,6 +191,24 @@ def compose_signatures():
     return {"bvg_compose": [S, S, C.POINTER(ComposeReport), C.POINTER(C.c_void_p)]}
 
 
+# the merge strategies of bvg_lgraph_union / _symmetrize and the `kind` of bvg_lgraph_filter (BVG_LMERGE_*, BVG_LFILTER_*)
+LMERGE_KEEP_FIRST, LMERGE_MIN, LMERGE_MAX = 0, 1, 2
+LFILTER_NO_LOOPS, LFILTER_SAME_CLASS, LFILTER_DIFFERENT_CLASS, LFILTER_LOWER_BOUND = 0, 1, 2, 3
+
+
+def labelled_signatures():
+    """argtypes of the bvg_lgraph_* entry points (arc-labelled graphs on the device), by name."""
+    vp, i64, u64, pp, ci = C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(C.c_void_p), C.c_int
+    N = C.POINTER(u64)
+    return {"bvg_lgraph_from_csr": [i64, vp, vp, vp, ci, ci, ci, pp], "bvg_lgraph_from_csr_dev": [i64, vp, vp, vp, ci, ci, ci, pp],
+            "bvg_lgraph_from_labelled": [vp, vp, pp], "bvg_lgraph_close": [vp],
+            "bvg_lgraph_info": [vp, C.POINTER(i64), N, C.POINTER(ci), C.POINTER(ci)],
+            "bvg_lgraph_get": [vp, vp, u64, vp, u64, vp, u64], "bvg_lgraph_get_dev": [vp, vp, u64, vp, u64, vp, u64],
+            "bvg_lgraph_underlying": [vp, pp], "bvg_lgraph_transpose": [vp, pp], "bvg_lgraph_union": [vp, vp, ci, pp],
+            "bvg_lgraph_symmetrize": [vp, ci, pp], "bvg_lgraph_filter": [vp, ci, vp, i64, i64, pp],
+            "bvg_lgraph_store_labels": [vp, pp, N, pp], "bvg_lgraph_store_labels_dev": [vp, vp, u64, N, vp]}
+
+
 OK, E_ARG, E_STATE, E_UNSUPPORTED, E_IO, E_EOF, E_NOMEM, E_HIP, E_CAPACITY = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 

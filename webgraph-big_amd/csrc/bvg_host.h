@@ -235,6 +235,22 @@ struct bvg_text {
     ~bvg_text() { (void)hipSetDevice(device); }
 };
 
+// arc labels stored as a bit stream, resident on the device (bvg_labels.hip; bvg_labelled.hip reads its class and decodes through it)
+struct bvg_labels {
+    int device = 0, kind = 0, width = 0;
+    int64_t nodes = 0;
+    uint64_t nbytes = 0, padded = 0;
+    DevArray<uint8_t> d_stream;
+    DevArray<uint64_t> d_offsets;
+    hipStream_t stream = nullptr;
+    DevArray<unsigned> d_err;
+    DevWorkspace cum_ws, tmp_ws;              // the prefix sums of a range and the scan's scratch (grown on demand)
+    ~bvg_labels() {
+        (void)hipSetDevice(device);
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+    }
+};
+
 namespace bvghost {
 
 // No C++ exception may cross the C ABI (a JVM behind JNI would be torn down by std::terminate): entry points that allocate

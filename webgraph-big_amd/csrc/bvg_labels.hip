@@ -24,21 +24,6 @@
 
 #include "bvg_host.h"
 
-struct bvg_labels {
-    int device = 0, kind = 0, width = 0;
-    int64_t nodes = 0;
-    uint64_t nbytes = 0, padded = 0;
-    DevArray<uint8_t> d_stream;
-    DevArray<uint64_t> d_offsets;
-    hipStream_t stream = nullptr;
-    DevArray<unsigned> d_err;
-    DevWorkspace cum_ws, tmp_ws;              // the prefix sums of a range and the scan's scratch (grown on demand)
-    ~bvg_labels() {
-        (void)hipSetDevice(device);
-        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
-    }
-};
-
 namespace bvg {
 namespace {
 

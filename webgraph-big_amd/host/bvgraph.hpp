@@ -421,6 +421,7 @@ public:
         return std::shared_ptr<BitStreamArcLabelledImmutableGraph>(new BitStreamArcLabelledImmutableGraph(g, l));
     }
     std::shared_ptr<BVGraph> underlying() const { return g_; }
+    bvg_labels* handle() const { return l_; }
     int64_t numNodes() const { return g_->numNodes(); }
     void decodeRange(int64_t from, int64_t to, std::vector<int32_t>& deg, std::vector<int64_t>& succ, std::vector<int32_t>& lab) {
         g_->decodeRange(from, to, deg, succ);
@@ -667,5 +668,85 @@ template <class G> std::vector<int64_t> permutation(G& g, int kind, uint64_t see
 template <class G> std::vector<int64_t> lexicographicalPermutation(G& g) { return permutation(g, BVG_PERM_LEX); }
 template <class G> std::vector<int64_t> grayCodePermutation(G& g) { return permutation(g, BVG_PERM_GRAY); }
 template <class G> std::vector<int64_t> randomPermutation(G& g, uint64_t seed) { return permutation(g, BVG_PERM_RANDOM, seed); }
+
+// ---- arc-labelled graphs on the device (bvg_lgraph_*): a CSR resident on the device plus one int label per arc and the label class
+// (BVG_LABEL_GAMMA_INT / BVG_LABEL_FIXED_INT).  The labelled half of Transform goes from LabelledGraph to LabelledGraph; storeLabels is
+// BitStreamArcLabelledImmutableGraph.store's label stream, written on the device
+class LabelledGraph {
+    bvg_lgraph* l_; int64_t n_ = 0; uint64_t m_ = 0; int kind_ = 0, width_ = 0;
+public:
+    explicit LabelledGraph(bvg_lgraph* l) : l_(l) {                          // owns l from here on: closed if the constructor fails
+        const int st = bvg_lgraph_info(l_, &n_, &m_, &kind_, &width_);
+        if (st != BVG_OK) { bvg_lgraph_close(l_); check(st, "lgraph_info"); }
+    }
+    LabelledGraph(const LabelledGraph&) = delete; LabelledGraph& operator=(const LabelledGraph&) = delete;
+    ~LabelledGraph() { bvg_lgraph_close(l_); }
+    // a resident graph over a CSR and its labels in host memory: the CSR validated as graphFromCSR validates it, every label against its class
+    static std::unique_ptr<LabelledGraph> fromCSR(const std::vector<uint64_t>& adjOff, const std::vector<int64_t>& adj, const std::vector<int32_t>& labels, int kind,
+                                                  int width = 0, int device = 0) {
+        if (adjOff.empty() || labels.size() != adj.size()) throw std::invalid_argument("LabelledGraph::fromCSR: adjOff holds nodes + 1 entries, labels one per arc");
+        bvg_lgraph* l = nullptr;
+        check(bvg_lgraph_from_csr((int64_t)adjOff.size() - 1, adjOff.data(), adj.empty() ? nullptr : adj.data(), labels.empty() ? nullptr : labels.data(), kind, width, device, &l),
+              "LabelledGraph::fromCSR");
+        return std::unique_ptr<LabelledGraph>(new LabelledGraph(l));
+    }
+    // a BitStreamArcLabelledImmutableGraph, decoded once
+    static std::unique_ptr<LabelledGraph> fromGraph(BitStreamArcLabelledImmutableGraph& g) {
+        bvg_lgraph* l = nullptr;
+        check(bvg_lgraph_from_labelled(g.underlying()->handle(), g.handle(), &l), "LabelledGraph::fromGraph");
+        return std::unique_ptr<LabelledGraph>(new LabelledGraph(l));
+    }
+    int64_t numNodes() const { return n_; }
+    int64_t numArcs() const { return (int64_t)m_; }
+    int kind() const { return kind_; }
+    int width() const { return width_; }
+    bvg_lgraph* handle() const { return l_; }
+    void csr(std::vector<uint64_t>& adjOff, std::vector<int64_t>& adj, std::vector<int32_t>& labels) const {
+        adjOff.resize((size_t)n_ + 1); adj.resize((size_t)m_); labels.resize((size_t)m_);
+        check(bvg_lgraph_get(l_, adjOff.data(), adjOff.size(), m_ ? adj.data() : nullptr, m_, m_ ? labels.data() : nullptr, m_), "lgraph_get");
+    }
+    // the unlabelled graph as a ParsedGraph of its own: every unlabelled transform and ParsedGraph::store apply to it
+    std::unique_ptr<ParsedGraph> underlying() const {
+        bvg_text* t = nullptr;
+        check(bvg_lgraph_underlying(l_, &t), "lgraph_underlying");
+        return std::unique_ptr<ParsedGraph>(new ParsedGraph(t));
+    }
+    // the bytes of basename.labels and the nodes + 1 label offsets (bit positions)
+    void storeLabels(std::vector<uint8_t>& stream, std::vector<uint64_t>& labelOffsets) const {
+        uint8_t* s = nullptr; uint64_t nb = 0; uint64_t* o = nullptr;
+        check(bvg_lgraph_store_labels(l_, &s, &nb, &o), "lgraph_store_labels");
+        stream.assign(s, s + nb); labelOffsets.assign(o, o + n_ + 1);
+        bvg_free(s); bvg_free(o);
+    }
+};
+inline std::unique_ptr<LabelledGraph> finishLabelled(int st, bvg_lgraph* l, const char* what) {
+    check(st, what);
+    return std::unique_ptr<LabelledGraph>(new LabelledGraph(l));
+}
+// Transform.transposeOffline on a labelled graph: arc (x, y) with label l becomes (y, x) with label l
+inline std::unique_ptr<LabelledGraph> transposeLabelled(const LabelledGraph& g) {
+    bvg_lgraph* l = nullptr;
+    const int st = bvg_lgraph_transpose(g.handle(), &l);
+    return finishLabelled(st, l, "transposeLabelled");
+}
+// Transform.union with a merge strategy (BVG_LMERGE_KEEP_FIRST / _MIN / _MAX): an arc of both gets merge(label_a, label_b)
+inline std::unique_ptr<LabelledGraph> unionLabelled(const LabelledGraph& a, const LabelledGraph& b, int strategy = BVG_LMERGE_KEEP_FIRST) {
+    bvg_lgraph* l = nullptr;
+    const int st = bvg_lgraph_union(a.handle(), b.handle(), strategy, &l);
+    return finishLabelled(st, l, "unionLabelled");
+}
+// Transform.symmetrizeOffline on a labelled graph: union(g, transpose(g), strategy)
+inline std::unique_ptr<LabelledGraph> symmetrizeLabelled(const LabelledGraph& g, int strategy = BVG_LMERGE_KEEP_FIRST) {
+    bvg_lgraph* l = nullptr;
+    const int st = bvg_lgraph_symmetrize(g.handle(), strategy, &l);
+    return finishLabelled(st, l, "symmetrizeLabelled");
+}
+// Transform.filterArcs with a LabelledArcFilter: kind = BVG_LFILTER_NO_LOOPS, _SAME_CLASS / _DIFFERENT_CLASS (nodeClass), or _LOWER_BOUND
+// (Transform.LowerBound as its code has it: label >= lowerBound stays)
+inline std::unique_ptr<LabelledGraph> filterLabelledArcs(const LabelledGraph& g, int kind, const std::vector<int64_t>& nodeClass = std::vector<int64_t>(), int64_t lowerBound = 0) {
+    bvg_lgraph* l = nullptr;
+    const int st = bvg_lgraph_filter(g.handle(), kind, nodeClass.empty() ? nullptr : nodeClass.data(), (int64_t)nodeClass.size(), lowerBound, &l);
+    return finishLabelled(st, l, "filterLabelledArcs");
+}
 
 }  // namespace webgraph
