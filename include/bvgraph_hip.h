@@ -727,7 +727,8 @@ int  bvg_compose(const bvg_transform_src* g0, const bvg_transform_src* g1, bvg_c
  * LIMITS: a source or a result of 2^31 arcs or more: BVG_E_UNSUPPORTED.  DEVICE MEMORY, besides sources and result: transpose 16 bytes per arc
  * plus the sort's workspace; union 4 bytes per arc of a and 16 per arc of b; symmetrize both, and the transpose itself; filter 12 per arc;
  * store_labels 12 per arc, 8 per node and the stream.  BVG_E_NOMEM leaves nothing allocated.
- * Not built: compose with a LabelSemiring, list labels through the transforms, user-written strategies and filters, several devices. */
+ * Not built: list labels through the transforms, user-written strategies, filters and semirings, several devices.  (The composition over a
+ * semiring is bvg_lcompose, below.) */
 typedef struct bvg_lgraph bvg_lgraph;
 enum { BVG_LMERGE_KEEP_FIRST = 0, BVG_LMERGE_MIN = 1, BVG_LMERGE_MAX = 2 };
 enum { BVG_LFILTER_NO_LOOPS = 0, BVG_LFILTER_SAME_CLASS = 1, BVG_LFILTER_DIFFERENT_CLASS = 2, BVG_LFILTER_LOWER_BOUND = 3 };
@@ -745,6 +746,47 @@ int  bvg_lgraph_symmetrize(const bvg_lgraph* src, int strategy, bvg_lgraph** out
 int  bvg_lgraph_filter(const bvg_lgraph* src, int kind, const int64_t* node_class, int64_t class_len, int64_t lower_bound, bvg_lgraph** out);
 int  bvg_lgraph_store_labels(const bvg_lgraph* l, uint8_t** stream, uint64_t* nbytes, uint64_t** label_offsets);
 int  bvg_lgraph_store_labels_dev(const bvg_lgraph* l, void* d_stream, uint64_t cap, uint64_t* nbytes, void* d_label_offsets);
+
+/* ---- Labelled compose (Transform.compose(ArcLabelledImmutableGraph, ArcLabelledImmutableGraph, LabelSemiring), T:1792-1918) ----
+ * The sparse matrix product of two arc-labelled graphs over a semiring.  The result has max(nodes0, nodes1) nodes; row x holds the successors
+ * z of bvg_compose's row x, and the label of (x, z) is the semiring's sum, over every y < nodes1 with x -> y in g0 and y -> z in g1, of
+ * label0(x, y) (x) label1(y, z).  An arc exists wherever the unlabelled product has one, whatever its label (the reference puts
+ * unconditionally, T:1849), so bvg_lgraph_underlying of the result is, for every semiring, bvg_compose of the sources' underlying graphs.
+ * SEMIRINGS: a LabelSemiring written by the user is Java code and cannot run on the device (as a LabelMergeStrategy cannot): the menu is
+ * BVG_SEMIRING_<ADD>_<MULTIPLY>.  MIN_PLUS is two-hop shortest paths (the reference's only test), PLUS_TIMES the ordinary matrix product, MAX_MIN
+ * the widest two-hop path.  Every `add` is commutative and associative on integers, so the result does not depend on the order in which the
+ * device meets the products: the call is deterministic.
+ * LABEL CLASS: sources whose (kind, width) differ or that live on different devices: BVG_E_ARG (T:1793).  The result keeps the sources' kind.
+ * BVG_LABEL_FIXED_INT: out_width in 0..31 is the result's width, -1 keeps the sources' (a (min, +) sum needs one bit more than its terms);
+ * BVG_LABEL_GAMMA_INT: out_width must be -1.  Any other out_width, an unknown semiring, a NULL handle or a NULL `out`: BVG_E_ARG, decided before
+ * any handle is looked at.
+ * ARITHMETIC (a deviation from the reference): the reference adds and multiplies Java ints and wraps silently.  Here every label is accumulated
+ * exactly in 64 bits, and a result label outside the result's class -- [0, 2^31 - 1] for gamma, [0, 2^out_width) for fixed -- refuses the call
+ * with BVG_E_ARG: nothing is written to *out, and the report holds how many arcs were out of range and the smallest (row, successor) among them
+ * (row first), which is as deterministic as the result.  PLUS_TIMES: every product is clamped to 2^32 before it is added; a key receives
+ * fewer than 2^31 products, so the sum stays below 2^63 and cannot wrap, and it is exact whenever it is in range (a clamped product alone
+ * is out of range).
+ * `report` (may be NULL) is filled on success and on the two refusals that come with data: the result refused for its size (arcs = the total
+ * that was refused) and the range refusal.
+ * LIMITS: those of bvg_compose -- a source or a result of 2^31 arcs or more, or 2^31 nodes or more: BVG_E_UNSUPPORTED.  The list label kinds:
+ * BVG_E_UNSUPPORTED.  *out is written on success only.
+ * DEVICE MEMORY, besides sources and result: 16 bytes per node (the rows' bounds, their lengths, the tier lists, the scan's temporaries) plus
+ * 8 bytes per row of tier 2, and tier 2's workspace: hash tables of 32 pow2ceil(min(bound, nodes)) bytes per row (a key and a 64-bit value a
+ * slot), as many rows side by side as fit 512 MiB (a row whose table alone is larger gets a workspace of that size); the host holds 12 bytes
+ * per node during the call.  BVG_E_NOMEM leaves nothing allocated.  A probe sequence that does not end within its table is BVG_E_HIP, never
+ * a spin. */
+enum { BVG_SEMIRING_MIN_PLUS = 0, BVG_SEMIRING_MAX_PLUS = 1, BVG_SEMIRING_MAX_MIN = 2, BVG_SEMIRING_MIN_MAX = 3, BVG_SEMIRING_PLUS_TIMES = 4 };   /* (add, multiply) */
+typedef struct bvg_lcompose_report {   /* 88 bytes */
+    uint64_t products;          /* as bvg_compose_report: sum of the rows' bounds */
+    uint64_t arcs;              /* of the result */
+    uint64_t rows[3];           /* rows with a bound > 0 that tier 0 / 1 / 2 took */
+    uint64_t limit[2];          /* the largest bound a row of tier 0 / tier 1 may have, in this build (a slot is 16 bytes here: not bvg_compose's) */
+    uint64_t batches;           /* launches of tier 2's batches per pass; 0 when no row needed it */
+    uint64_t out_of_range;      /* arcs whose label is outside the result's class; 0 on success */
+    int64_t  first_row;         /* the smallest (row, successor) among them, row first; -1, -1 when there is none */
+    int64_t  first_successor;
+} bvg_lcompose_report;
+int  bvg_lcompose(const bvg_lgraph* g0, const bvg_lgraph* g1, int semiring, int out_width, bvg_lcompose_report* report, bvg_lgraph** out);
 
 /* ---- synthetic-workload helper (bench only): K back-to-back copies of the graph ----
  * BV records are translation invariant (every value is coded relative to the node id, Appendix A.3

@@ -27,4 +27,5 @@ from .transform import (identity_graph, map_graph, filter_arcs, transpose_graph,
                         lexicographical_permutation, gray_code_permutation, random_permutation, permutation_dev, load_longs, store_longs, transform_main, compose, compose_main)
 from . import labelled  # noqa: F401,E402
 from .labelled import (LabelledGraph, transpose_labelled, union_labelled, symmetrize_labelled, filter_labelled_arcs, label_spec,  # noqa: F401,E402
-                       labelled_transform_main)
+                       labelled_transform_main, compose_labelled, labelled_compose_main, SEMIRING_MIN_PLUS, SEMIRING_MAX_PLUS, SEMIRING_MAX_MIN,
+                       SEMIRING_MIN_MAX, SEMIRING_PLUS_TIMES)

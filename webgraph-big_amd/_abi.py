@@ -209,6 +209,26 @@ def labelled_signatures():
             "bvg_lgraph_store_labels": [vp, pp, N, pp], "bvg_lgraph_store_labels_dev": [vp, vp, u64, N, vp]}
 
 
+# the semirings of bvg_lcompose (BVG_SEMIRING_<ADD>_<MULTIPLY>)
+SEMIRING_MIN_PLUS, SEMIRING_MAX_PLUS, SEMIRING_MAX_MIN, SEMIRING_MIN_MAX, SEMIRING_PLUS_TIMES = 0, 1, 2, 3, 4
+
+
+class LComposeReport(C.Structure):
+    """bvg_lcompose_report (88 bytes): bvg_compose_report's fields, then the range refusal's."""
+    _fields_ = [("products", C.c_uint64), ("arcs", C.c_uint64), ("rows", C.c_uint64 * 3), ("limit", C.c_uint64 * 2), ("batches", C.c_uint64),
+                ("out_of_range", C.c_uint64), ("first_row", C.c_int64), ("first_successor", C.c_int64)]
+
+    def as_dict(self):
+        return {"products": int(self.products), "arcs": int(self.arcs), "rows": [int(v) for v in self.rows], "limit": [int(v) for v in self.limit], "batches": int(self.batches),
+                "out_of_range": int(self.out_of_range), "first_row": int(self.first_row), "first_successor": int(self.first_successor)}
+
+
+def lcompose_signatures():
+    """argtypes of bvg_lcompose, by name (a group of its own: labelled_signatures() is the set of the bvg_lgraph_* names)."""
+    vp, ci = C.c_void_p, C.c_int
+    return {"bvg_lcompose": [vp, vp, ci, ci, C.POINTER(LComposeReport), C.POINTER(C.c_void_p)]}
+
+
 OK, E_ARG, E_STATE, E_UNSUPPORTED, E_IO, E_EOF, E_NOMEM, E_HIP, E_CAPACITY = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 

@@ -24,32 +24,11 @@
 #include <cstdint>
 
 #include "bvg_host.h"
+#include "bvg_compose_shared.h"
 #include "../../include/bvgraph_hip.h"
 
 namespace bvghost {
 namespace {
-
-constexpr uint64_t kMaxElems = 0x7FFFFFFFull;      // what one prefix sum (launch_exclusive_scan) takes
-constexpr unsigned long long kEmpty = ~0ull;       // no node id: a slot without a key, and the key that sorts behind every node
-constexpr uint32_t kSlots0 = 512, kSlots1 = 8192;  // keys of an LDS table: 4 KiB per wavefront, 64 KiB per workgroup
-constexpr uint64_t kLimit0 = kSlots0 / 2, kLimit1 = kSlots1 / 2;
-constexpr int kThreads0 = 64, kThreads1 = 512, kThreads2 = 512;
-constexpr uint32_t kMinSlots = 64;                 // of an LDS table
-constexpr uint64_t kDefaultBudget = 256ull << 20;  // bytes of tier 2's workspace
-constexpr unsigned kMaxGrid = 1u << 16;            // workgroups of a launch; each strides over its rows
-
-__host__ __device__ __forceinline__ uint64_t pow2ceil(uint64_t v) { uint64_t p = 1; while (p < v) p <<= 1; return p; }
-__host__ __device__ __forceinline__ uint64_t table_slots2(uint64_t ub, int64_t n) { return 2 * pow2ceil(ub < (uint64_t)n ? ub : (uint64_t)n); }   // tier 2
-
-struct ComposeArgs {
-    const uint64_t* off0; const int64_t* adj0; int64_t n0;
-    const uint64_t* off1; const int64_t* adj1; int64_t n1;
-    int64_t n;
-    const uint64_t* ub;              // [n]
-    int32_t* cnt;                    // [n] the rows' lengths (symbolic pass)
-    const uint64_t* out_off; int64_t* out_adj;   // the result (numeric pass)
-    unsigned* err;                   // [0] a probe cap was hit, [1] a row's two passes disagree
-};
 
 // ---- stage 1
 __global__ void compose_bound_kernel(ComposeArgs a, uint64_t* ub) {
@@ -60,38 +39,6 @@ __global__ void compose_bound_kernel(ComposeArgs a, uint64_t* ub) {
             if (y >= 0 && y < a.n1) s += a.off1[y + 1] - a.off1[y];
         }
         ub[x] = s;
-    }
-}
-
-// ---- the table.  1: z is new, 0: it was there (or the cap was hit: flagged)
-__device__ __forceinline__ int table_insert(unsigned long long* tab, uint64_t mask, unsigned bits, unsigned long long z, unsigned* err) {
-    uint64_t i = ((z * 0x9E3779B97F4A7C15ull) >> (64u - bits)) & mask;       // multiplicative: the high bits depend on every bit of z
-    for (uint64_t step = 0; step <= mask; step++, i = (i + 1) & mask) {
-        const unsigned long long old = atomicCAS(&tab[i], kEmpty, z);
-        if (old == kEmpty) return 1;
-        if (old == z) return 0;
-    }
-    atomicOr(err, 1u);
-    return 0;
-}
-
-// a[0, len) ascending, by the whole workgroup: the bitonic network whose every comparison puts the smaller key at the lower index
-// (a flip, then halving strides), so positions at and beyond len stand for keys above all others and are never touched
-template <int THREADS> __device__ __forceinline__ void group_sort(unsigned long long* a, uint64_t len) {
-    const uint64_t p = pow2ceil(len);
-    for (uint64_t k = 2; k <= p; k <<= 1) {
-        for (uint64_t j = k >> 1; j > 0; j >>= 1) {
-            const bool flip = j == (k >> 1);
-            for (uint64_t t = threadIdx.x; t < (p >> 1); t += THREADS) {
-                const uint64_t lo = (t / j) * (j << 1) + (t % j);
-                const uint64_t hi = flip ? ((lo & ~(k - 1)) | ((k - 1) - (lo & (k - 1)))) : lo + j;
-                if (hi < len) {
-                    const unsigned long long u = a[lo], v = a[hi];
-                    if (u > v) { a[lo] = v; a[hi] = u; }
-                }
-            }
-            __syncthreads();
-        }
     }
 }
 
@@ -180,10 +127,6 @@ __global__ void __launch_bounds__(THREADS) compose_rows_kernel(ComposeArgs a, co
     }
 }
 
-uint64_t knob_u64(const char* name, uint64_t dflt) { const char* v = knob(name); return v && *v ? strtoull(v, nullptr, 10) : dflt; }
-
-struct Tier2Batch { uint32_t lo, hi; uint64_t slots; };   // rows [lo, hi) of tier 2's list, and the slots of their tables together
-
 // both passes over the three tiers' lists (d_rows: tier 0's, tier 1's, tier 2's rows one after another)
 int run_pass(const ComposeArgs& a, const uint32_t* d_rows, const uint64_t count[3], const std::vector<Tier2Batch>& batches, unsigned long long* ws, const uint64_t* d_tab_off, int numeric) {
     auto blocks = [](uint64_t rows) { return dim3((unsigned)(rows < kMaxGrid ? rows : kMaxGrid)); };
@@ -229,29 +172,16 @@ int compose_csr(const Source& g0, const Source& g1, bvg_compose_report* report, 
         std::vector<uint64_t> h_ub((size_t)n);
         HIPCHK(hipMemcpy(h_ub.data(), ub.get(), (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
         if (dbgt) ms_bound = sw.lap();
-        auto tier_of = [&](uint64_t u) { int tr = u <= kLimit0 ? 0 : u <= kLimit1 ? 1 : 2; return forced > tr ? forced : tr; };
-        for (int64_t x = 0; x < n; x++) if (h_ub[(size_t)x]) { rep.products += h_ub[(size_t)x]; count[tier_of(h_ub[(size_t)x])]++; }
-        std::vector<uint32_t> h_rows((size_t)(count[0] + count[1] + count[2]));
-        uint64_t at[3] = {0, count[0], count[0] + count[1]};
-        for (int64_t x = 0; x < n; x++) if (h_ub[(size_t)x]) h_rows[(size_t)at[tier_of(h_ub[(size_t)x])]++] = (uint32_t)x;
-        for (int i = 0; i < 3; i++) rep.rows[i] = count[i];
-        if (!h_rows.empty()) HIPCHK(hipMemcpy(rows.get(), h_rows.data(), h_rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        TierPlan plan;
+        plan_tiers(h_ub, n, kLimit0, kLimit1, forced, budget / sizeof(unsigned long long), plan);
+        rep.products = plan.products;
+        for (int i = 0; i < 3; i++) rep.rows[i] = count[i] = plan.count[i];
+        if (!plan.rows.empty()) HIPCHK(hipMemcpy(rows.get(), plan.rows.data(), plan.rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         // tier 2's batches: tables side by side in the workspace, as many rows as the budget holds
-        uint64_t ws_slots = 0;
+        batches = std::move(plan.batches);
         if (count[2]) {
-            const uint64_t cap = budget / sizeof(unsigned long long);
-            std::vector<uint64_t> h_tab((size_t)count[2]);
-            const uint32_t* r2 = h_rows.data() + count[0] + count[1];
-            Tier2Batch b{0, 0, 0};
-            for (uint32_t i = 0; i < (uint32_t)count[2]; i++) {
-                const uint64_t slots = table_slots2(h_ub[r2[i]], n);
-                if (b.hi > b.lo && b.slots + slots > cap) { batches.push_back(b); b = Tier2Batch{i, i, 0}; }
-                h_tab[i] = b.slots; b.slots += slots; b.hi = i + 1;
-            }
-            batches.push_back(b);
-            for (const Tier2Batch& q : batches) if (q.slots > ws_slots) ws_slots = q.slots;
-            if (ws.alloc((size_t)ws_slots) || tab_off.alloc((size_t)count[2])) return BVG_E_NOMEM;
-            HIPCHK(hipMemcpy(tab_off.get(), h_tab.data(), h_tab.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+            if (ws.alloc((size_t)plan.ws_slots) || tab_off.alloc((size_t)count[2])) return BVG_E_NOMEM;
+            HIPCHK(hipMemcpy(tab_off.get(), plan.tab.data(), plan.tab.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
         }
         rep.batches = batches.size();
         if (dbgt) ms_tiers = sw.lap();
@@ -286,6 +216,13 @@ int compose_csr(const Source& g0, const Source& g1, bvg_compose_report* report, 
 }
 
 }  // namespace
+
+// what bvg_lcompose.hip runs of the above as it is (bvg_compose_shared.h)
+void compose_launch_bounds(const ComposeArgs& a, uint64_t* ub) { hipLaunchKernelGGL(compose_bound_kernel, dim3(grid(a.n, 256)), dim3(256), 0, 0, a, ub); }
+int compose_symbolic_pass(const ComposeArgs& a, const uint32_t* d_rows, const uint64_t count[3], const std::vector<Tier2Batch>& batches, unsigned long long* ws, const uint64_t* d_tab_off) {
+    return run_pass(a, d_rows, count, batches, ws, d_tab_off, 0);
+}
+
 }  // namespace bvghost
 
 extern "C" int bvg_compose(const bvg_transform_src* g0, const bvg_transform_src* g1, bvg_compose_report* report, bvg_text** out) {

@@ -251,6 +251,13 @@ struct bvg_labels {
     }
 };
 
+// an arc-labelled graph as a CSR in HBM (bvg_labelled.hip, bvg_lcompose.hip)
+struct bvg_lgraph {
+    std::unique_ptr<bvg_text> g;        // the underlying graph
+    DevArray<int32_t> d_lab;            // labels[arcs], in successor order
+    int kind = 0, width = 0;
+};
+
 namespace bvghost {
 
 // No C++ exception may cross the C ABI (a JVM behind JNI would be torn down by std::terminate): entry points that allocate

@@ -29,12 +29,6 @@
 #include "bvg_host.h"
 #include "../../include/bvgraph_hip.h"
 
-struct bvg_lgraph {
-    std::unique_ptr<bvg_text> g;        // the underlying graph
-    DevArray<int32_t> d_lab;            // labels[arcs], in successor order
-    int kind = 0, width = 0;
-};
-
 namespace bvghost {
 namespace {
 

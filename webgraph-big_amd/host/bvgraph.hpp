@@ -735,6 +735,17 @@ inline std::unique_ptr<LabelledGraph> unionLabelled(const LabelledGraph& a, cons
     const int st = bvg_lgraph_union(a.handle(), b.handle(), strategy, &l);
     return finishLabelled(st, l, "unionLabelled");
 }
+// Transform.compose with a LabelSemiring (bvg_lcompose): the successors of composeGraphs on the underlying graphs, and on (x, z) the semiring's sum
+// over every y with x -> y in a and y -> z in b of label_a(x, y) (x) label_b(y, z).  outWidth: the width of a FixedWidthIntLabel result (-1: the
+// sources').  Exact arithmetic: a label outside the result's class throws std::invalid_argument, with the count and the first such arc in *report
+enum Semiring { SEMIRING_MIN_PLUS = BVG_SEMIRING_MIN_PLUS, SEMIRING_MAX_PLUS = BVG_SEMIRING_MAX_PLUS, SEMIRING_MAX_MIN = BVG_SEMIRING_MAX_MIN,
+                SEMIRING_MIN_MAX = BVG_SEMIRING_MIN_MAX, SEMIRING_PLUS_TIMES = BVG_SEMIRING_PLUS_TIMES };
+typedef bvg_lcompose_report LabelledComposeReport;
+inline std::unique_ptr<LabelledGraph> composeLabelled(const LabelledGraph& a, const LabelledGraph& b, Semiring semiring, int outWidth = -1, LabelledComposeReport* report = nullptr) {
+    bvg_lgraph* l = nullptr;
+    const int st = bvg_lcompose(a.handle(), b.handle(), (int)semiring, outWidth, report, &l);
+    return finishLabelled(st, l, "composeLabelled");
+}
 // Transform.symmetrizeOffline on a labelled graph: union(g, transpose(g), strategy)
 inline std::unique_ptr<LabelledGraph> symmetrizeLabelled(const LabelledGraph& g, int strategy = BVG_LMERGE_KEEP_FIRST) {
     bvg_lgraph* l = nullptr;

@@ -2,7 +2,8 @@
 per arc and the label class (GammaCodedIntLabel / FixedWidthIntLabel).  Transform's labelled half -- transpose, union and symmetrise under a
 merge strategy, filterArcs with a LabelledArcFilter -- goes from LabelledGraph to LabelledGraph; the label stream is written on the device
 (BitStreamArcLabelledImmutableGraph.store) and write() leaves the files BitStreamArcLabelledImmutableGraph.load reads; and the labelled part of
-the command line of Transform.main (Transform.java:2295-2297, :2326-2328, :2372-2378)."""
+the command line of Transform.main (Transform.java:2295-2297, :2326-2328, :2372-2378).  compose_labelled is Transform.compose with a LabelSemiring
+(bvg_lcompose): the product of two labelled graphs over one of a fixed menu of semirings, with a command line of its own."""
 import ctypes as C
 import os
 import re
@@ -20,6 +21,9 @@ _STRATEGIES = {KEEP_FIRST: _abi.LMERGE_KEEP_FIRST, MIN: _abi.LMERGE_MIN, MAX: _a
 _FILTERS = {"NO_LOOPS": _abi.LFILTER_NO_LOOPS, "SAME_CLASS": _abi.LFILTER_SAME_CLASS, "DIFFERENT_CLASS": _abi.LFILTER_DIFFERENT_CLASS,
             LOWER_BOUND: _abi.LFILTER_LOWER_BOUND}
 _LABEL_CLASSES = {LABEL_GAMMA_INT: "GammaCodedIntLabel", LABEL_FIXED_INT: "FixedWidthIntLabel"}
+SEMIRING_MIN_PLUS, SEMIRING_MAX_PLUS, SEMIRING_MAX_MIN, SEMIRING_MIN_MAX, SEMIRING_PLUS_TIMES = (
+    _abi.SEMIRING_MIN_PLUS, _abi.SEMIRING_MAX_PLUS, _abi.SEMIRING_MAX_MIN, _abi.SEMIRING_MIN_MAX, _abi.SEMIRING_PLUS_TIMES)
+_SEMIRINGS = {"MIN_PLUS": SEMIRING_MIN_PLUS, "MAX_PLUS": SEMIRING_MAX_PLUS, "MAX_MIN": SEMIRING_MAX_MIN, "MIN_MAX": SEMIRING_MIN_MAX, "PLUS_TIMES": SEMIRING_PLUS_TIMES}
 UNDERLYINGGRAPH_SUFFIX = "-underlying"      # ArcLabelledImmutableGraph.UNDERLYINGGRAPH_SUFFIX
 
 
@@ -233,6 +237,53 @@ def filter_labelled_arcs(g, kind, node_class=None, lower_bound=None):
         return LabelledGraph(h, s._device)
 
 
+def _lcompose_fns():
+    """bvg_lcompose, bound on first use."""
+    L = _labelled_fns()
+    if getattr(L, "_lcompose_bound", False):
+        return L
+    for name, args in _abi.lcompose_signatures().items():
+        if not hasattr(L, name):
+            raise UnsupportedOperationException(_abi.E_UNSUPPORTED, name + " is not in this build of the library")
+        getattr(L, name).argtypes = args
+    L._lcompose_bound = True
+    return L
+
+
+def _semiring(s):
+    if isinstance(s, str) and s in _SEMIRINGS:
+        return _SEMIRINGS[s]
+    if isinstance(s, (int, np.integer)) and not isinstance(s, bool) and int(s) in _SEMIRINGS.values():
+        return int(s)
+    raise IllegalArgumentException(_abi.E_ARG, "unknown semiring %r: one of %s" % (s, ", ".join(sorted(_SEMIRINGS))))
+
+
+def compose_labelled(a, b, semiring, out_width=None, report=False):
+    """Transform.compose(a, b, semiring): the successors of the unlabelled product, and on (x, z) the semiring's sum over every y with x -> y
+    in a and y -> z in b of label_a(x, y) (x) label_b(y, z).  semiring: "MIN_PLUS", "MAX_PLUS", "MAX_MIN", "MIN_MAX", "PLUS_TIMES" (add, multiply)
+    or its SEMIRING_* number.  out_width: the width of a FixedWidthIntLabel result (None keeps the sources').  The arithmetic is exact: a label
+    outside the result's class raises IllegalArgumentException with .report, .out_of_range and .first_arc = the smallest (row, successor) among
+    them; a result refused for its size raises UnsupportedOperationException with .report.  report=True: (graph, dict of bvg_lcompose_report)."""
+    sr = _semiring(semiring)
+    if out_width is not None and not (isinstance(out_width, (int, np.integer)) and 0 <= int(out_width) <= 31):
+        raise IllegalArgumentException(_abi.E_ARG, "out_width is None or in 0..31, not %r" % (out_width,))
+    with _LSource(a) as sa, _LSource(b) as sb:
+        h, rep = C.c_void_p(), _abi.LComposeReport()
+        st = _lcompose_fns().bvg_lcompose(sa._h, sb._h, sr, -1 if out_width is None else int(out_width), C.byref(rep), C.byref(h))
+        if st == _abi.E_ARG and rep.out_of_range:
+            e = IllegalArgumentException(st, "compose_labelled: %d labels outside the result's class, the first on arc (%d, %d)"
+                                         % (rep.out_of_range, rep.first_row, rep.first_successor))
+            e.report, e.out_of_range, e.first_arc = rep.as_dict(), int(rep.out_of_range), (int(rep.first_row), int(rep.first_successor))
+            raise e
+        try:
+            _check(st, "compose_labelled")
+        except UnsupportedOperationException as e:
+            e.report = rep.as_dict()
+            raise
+        g = LabelledGraph(h, sa._device)
+        return (g, rep.as_dict()) if report else g
+
+
 # ---- Transform.main, the labelled transforms
 
 _LARITY = {"transposeOffline": (2, 2), "symmetrizeOffline": (3, 3), "union": (4, 4), "larcfilter": (3, 3)}
@@ -308,6 +359,48 @@ def labelled_transform_main(argv=None):
         else:
             result = filter_labelled_arcs(sources[0], "NO_LOOPS")
         result.write(dest)
+    finally:
+        if result is not None:
+            result.close()
+        for s in sources:
+            s.close()
+        for g in opened:
+            g.close()
+            g.g.close()
+    return 0
+
+
+# ---- the labelled composition's command line
+
+def labelled_compose_arg_parser():
+    import argparse
+    ap = argparse.ArgumentParser(prog="labelled_compose_main", description="Composes two arc-labelled graphs on the device (Transform.compose with a "
+                                 "LabelSemiring): source0 source1 dest SEMIRING.  SEMIRING (add_multiply): " + ", ".join(sorted(_SEMIRINGS)) + ".")
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--width", type=int, default=None, help="the width of a FixedWidthIntLabel result (default: the sources')")
+    ap.add_argument("param", nargs="*")
+    return ap
+
+
+def labelled_compose_main(argv=None):
+    """[--device N] source0 source1 dest SEMIRING [--width W]: loads two BitStreamArcLabelledImmutableGraphs and write()s their composition.
+    Returns 0, or 1 after a message for a wrong number of parameters or an unknown semiring."""
+    a = labelled_compose_arg_parser().parse_args(argv)
+    p = a.param
+    if len(p) != 4:
+        print("labelled_compose_main: I need 4 arguments rather than %d." % len(p), file=sys.stderr)
+        return 1
+    if p[3] not in _SEMIRINGS:
+        print("labelled_compose_main: unknown semiring %r: one of %s" % (p[3], ", ".join(sorted(_SEMIRINGS))), file=sys.stderr)
+        return 1
+    opened, sources, result = [], [], None
+    try:
+        for name in p[:2]:
+            g = BitStreamArcLabelledImmutableGraph.load(name, a.device)
+            opened.append(g)
+            sources.append(LabelledGraph.from_graph(g, a.device))
+        result = compose_labelled(sources[0], sources[1], p[3], out_width=a.width)
+        result.write(p[2])
     finally:
         if result is not None:
             result.close()
