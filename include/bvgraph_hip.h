@@ -557,7 +557,7 @@ int bvg_ef_store(int64_t nodes, int64_t upper_bound, int log2_quantum, int big_e
  * An arc list: every line holds two numbers or none; a line whose first byte is '#' is skipped whole (ScatteredArcsASCIIGraph); `shift` is
  * added to both ends; sources in any order; a duplicate arc appears once; nodes = max(largest id + 1, min_nodes); an empty text gives
  * min_nodes nodes and no arcs.  BVG_TEXT_SYMMETRIZE adds the reverse of every arc, BVG_TEXT_NO_LOOPS drops the arcs x -> x (the two
- * switches of ScatteredArcsASCIIGraph); unknown flag bits: BVG_E_ARG.  Not built: identifiers that are not node numbers.  Refused besides
+ * switches of ScatteredArcsASCIIGraph); unknown flag bits: BVG_E_ARG.  Identifiers that are not node numbers: "scattered arc lists" below.  Refused besides
  * BVG_TEXT_BAD_BYTE and BVG_TEXT_TOO_LARGE:
  *   BVG_TEXT_SHIFT_RANGE     BVG_E_ARG  id + shift below 0 or above 2^63 - 1 (AL:157); at the first byte of the number (a shift of -2^63 is
  *                                       BVG_E_ARG for every entry point that takes one, before anything is read)
@@ -608,6 +608,63 @@ int  bvg_text_format_arcs(bvg_graph* g, int64_t from, int64_t to, int64_t shift,
 int  bvg_text_format_arcs_dev(bvg_graph* g, int64_t from, int64_t to, int64_t shift, void* d_out, uint64_t cap, uint64_t* nbytes);
 int  bvg_text_format_csr(int kind, int64_t first_node, int64_t nodes, const uint64_t* adj_off, const int64_t* adj, int64_t shift,
                          void* out, uint64_t cap, uint64_t* nbytes);
+
+/* ---- scattered arc lists (ScatteredArcsASCIIGraph.java, "SA"): arc lists whose identifiers are not node numbers ----
+ * Every newly seen identifier gets the next node number, offending lines are counted and skipped, and the identifiers in order of
+ * appearance stay with the result (ids[node]; basename.ids).  The result is a bvg_text: bvg_text_info / _get / _get_dev / _store / _close
+ * and every bvg_transform_* call and bvg_compose take it.
+ * LINES end at "\r", "\n" or "\r\n" (the rule of the text graphs above); a last line without a terminator counts.  WHITESPACE is every
+ * byte 0..32; a TOKEN is a maximal run of other bytes (bytes >= 0x80 belong to tokens).  A line of whitespace only is skipped; a line
+ * whose very first byte is '#' is a comment (" #x 1" is not: its source "#x" is a bad token).
+ * An IDENTIFIER is an optional '-' followed by decimal digits, of a value in [-2^63, 2^63); leading zeros do not count; a lone "-" is 0, as
+ * in the reference (SA:869-887).  "+1", "--1", "1-", "1x" are bad tokens.  A token is read from left to right and the first thing wrong
+ * with it decides: a byte that is no digit makes it BAD, a 20th significant digit or (at its end) a value outside the range makes it
+ * TOO_LARGE.  DELIBERATE DEVIATION: the reference wraps around silently on overflow; here such a token is refused, not wrapped.
+ * PER LINE, in this order (SA:495-654): a bad source -- the line is ignored, its target is NOT registered even if valid; a good source
+ * is registered as a node, also when no target follows (NO_TARGET) or the target is bad (BAD_TARGET), and such a line adds no arc; a good
+ * source and a good target -- the target is registered and the arc kept; further tokens on the line count as TRAILING, the arc is kept.
+ * BVG_TEXT_NO_LOOPS drops x -> x after both ends are registered ("5 5" alone: one node, no arc); BVG_TEXT_SYMMETRIZE adds the reverse
+ * of every kept arc; a duplicate arc appears once.
+ * NODE NUMBERS.  An identifier's node number is the rank of its first occurrence among all first occurrences; ids[node] is the
+ * identifier; nodes = the distinct registered identifiers.  Nothing depends on the order in which the device gets to the lines.
+ * GIVEN NUMBERING (known_ids != NULL; the reference's translation function, for numeric identifiers): node i has identifier known_ids[i],
+ * nodes = n_known whatever the text mentions (an identifier never mentioned is an isolated node), ids = known_ids.  A line of two
+ * identifiers whose source is not among them is skipped and counted as UNKNOWN_SOURCE, else one whose target is not as UNKNOWN_TARGET
+ * (a line that is NO_TARGET, BAD_TARGET or TOO_LARGE is that, whoever its source is).  A value that occurs twice
+ * in known_ids: BVG_E_ARG.  known_ids == NULL with n_known > 0, or n_known < 0: BVG_E_ARG.
+ * THE REPORT (rep may be NULL): lines = the line breaks, plus one when bytes follow the last of them; arcs = the lines whose arc was
+ * kept (before the reverse arcs are added and duplicates removed; dropped loops are not in it); one count per category, every line in at
+ * most one of bad_source, bad_target, no_target, too_large, unknown_source, unknown_target (too_large: the source or the target is
+ * TOO_LARGE) and besides that in trailing when it has more than two tokens and both ends are identifiers; first_byte / first_line /
+ * first_reason: the offending line (any category but TRAILING, which is a warning) of the smallest byte offset -- the offset of the
+ * token at fault, of the source for NO_TARGET -- and first_reason = 0 when there is none.
+ * BVG_TEXT_STRICT: an offending line refuses the call, BVG_E_IO, with that position and reason (BVG_SCATTERED_*) in *err, *out = NULL;
+ * the report is filled all the same.  Unknown flag bits: BVG_E_ARG.
+ * bvg_scattered_ids / _ids_dev: ids[nodes], under the capacity contract of bvg_text_get; BVG_E_UNSUPPORTED on a bvg_text that has none
+ * (every other producer's).
+ * DEVICE MEMORY on top of the text: 16 bytes per token and 32 per line while the lines are classified; then 16 bytes per occurrence
+ * (a registered end of a line) plus a table of 16-byte slots, a power of two of at least 4/3 of the occurrences (21 to 43 bytes per
+ * occurrence), 32 bytes per distinct identifier plus the sort's workspace while they are numbered, and 20 bytes per arc; then what an arc
+ * list takes while it is sorted (44 bytes per arc, 88 with BVG_TEXT_SYMMETRIZE).  What stays in the object: 8 (nodes + 1) + 8 arcs +
+ * 8 nodes.  Limits: a text of 8 TiB, 2^31 lines, 2^31 occurrences or 2^31 pairs (2^30 arcs with BVG_TEXT_SYMMETRIZE) or more:
+ * BVG_E_UNSUPPORTED.  String identifiers (URLs) are not built. */
+typedef struct bvg_scattered_report {       /* 104 bytes */
+    uint64_t lines, arcs;
+    uint64_t bad_source, bad_target, no_target, too_large, trailing, unknown_source, unknown_target, dropped_loops;
+    uint64_t first_byte;                    /* the first offending line: offset of the token at fault */
+    int64_t  first_line;                    /* 1-based; 0 when there is none */
+    int32_t  first_reason;                  /* BVG_SCATTERED_BAD_SOURCE ...; 0 when there is none */
+    int32_t  reserved;
+} bvg_scattered_report;
+enum { BVG_SCATTERED_BAD_SOURCE = 1, BVG_SCATTERED_BAD_TARGET = 2, BVG_SCATTERED_NO_TARGET = 3, BVG_SCATTERED_TOO_LARGE = 4,
+       BVG_SCATTERED_TRAILING = 5, BVG_SCATTERED_UNKNOWN_SOURCE = 6, BVG_SCATTERED_UNKNOWN_TARGET = 7 };
+#define BVG_TEXT_STRICT     4u
+int  bvg_scattered_parse(const void* text, uint64_t nbytes, uint32_t flags, const int64_t* known_ids, int64_t n_known, int device,
+                         bvg_text** out, bvg_scattered_report* rep, bvg_text_error* err);
+int  bvg_scattered_parse_dev(const void* d_text, uint64_t nbytes, uint32_t flags, const void* d_known_ids, int64_t n_known, int device,
+                             bvg_text** out, bvg_scattered_report* rep, bvg_text_error* err);
+int  bvg_scattered_ids(bvg_text* t, int64_t* ids, uint64_t cap);
+int  bvg_scattered_ids_dev(bvg_text* t, void* d_ids, uint64_t cap);
 
 /* ---- Transform (Transform.java, "T"): map, filter, transpose, symmetrise, union, and the lex / Gray / random permutations ----
  * Every graph-valued call returns the CSR-in-HBM handle of the text graphs above (bvg_text): bvg_text_info / _get / _get_dev / _store /

@@ -6,7 +6,7 @@ shard helpers bench.py and the tests share); experimental/ holds kernels that lo
 `make experimental`.  The CPU encoder and the synthetic graph generators are test tooling and live outside the package (tooling/).
 """
 from ._abi import *  # noqa: F401,F403
-from ._abi import Params, ScanResult, Tuning, StatsSummary, EFParams, TextError, TransformSrc, ComposeReport, default_params  # noqa: F401
+from ._abi import Params, ScanResult, Tuning, StatsSummary, EFParams, TextError, ScatteredReport, TransformSrc, ComposeReport, default_params  # noqa: F401
 from .bvgraph import (BVGraph, NodeIterator, LazyLongIterator, BVGraphError, IllegalArgumentException,  # noqa: F401
                       IllegalStateException, UnsupportedOperationException, IOException, EOFException, DeviceError,
                       NoSuchElementException, parse_properties, decode_offsets, arc_mix, build, lib, library_path,
@@ -21,7 +21,8 @@ from .bvgraph import (BVGraph, NodeIterator, LazyLongIterator, BVGraphError, Ill
 from .efgraph import EFGraph, parse_ef_properties, derive_ef_offsets, store_efgraph, write_efgraph, efgraph_main  # noqa: F401,E402
 from . import textgraph  # noqa: F401,E402
 from .textgraph import (ParsedGraph, parse_ascii_graph, parse_arc_list, parse_ascii_graph_dev, parse_arc_list_dev, load_ascii_graph, load_arc_list,  # noqa: F401,E402
-                        format_csr, write_bvgraph, coded_gaps, asciigraph_main, arclist_main, bvgraph_main)
+                        format_csr, write_bvgraph, coded_gaps, asciigraph_main, arclist_main, bvgraph_main,
+                        ScatteredGraph, parse_scattered_arcs, parse_scattered_arcs_dev, load_scattered_arcs, scattered_main)
 from . import transform  # noqa: F401,E402
 from .transform import (identity_graph, map_graph, filter_arcs, transpose_graph, symmetrize_graph, simplify_graph, union, remove_dangling,  # noqa: F401,E402
                         lexicographical_permutation, gray_code_permutation, random_permutation, permutation_dev, load_longs, store_longs, transform_main, compose, compose_main)

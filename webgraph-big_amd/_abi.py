@@ -155,6 +155,30 @@ def text_signatures():
             "bvg_text_format_csr": [ci, i64, i64, vp, vp, i64, vp, u64, N]}
 
 
+class ScatteredReport(C.Structure):
+    """bvg_scattered_report (104 bytes): what bvg_scattered_parse saw in the text."""
+    _fields_ = ([(k, C.c_uint64) for k in ("lines", "arcs", "bad_source", "bad_target", "no_target", "too_large", "trailing", "unknown_source", "unknown_target",
+                                           "dropped_loops", "first_byte")]
+                + [("first_line", C.c_int64), ("first_reason", C.c_int32), ("reserved", C.c_int32)])
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+        d["first_reason"] = SCATTERED_REASONS.get(d["first_reason"])
+        return d
+
+
+# bvg_scattered_report.first_reason and, under TEXT_STRICT_FLAG, bvg_text_error.reason (BVG_SCATTERED_BAD_SOURCE ...); the flag itself (BVG_TEXT_STRICT)
+SCATTERED_REASONS = {1: "bad_source", 2: "bad_target", 3: "no_target", 4: "too_large", 5: "trailing", 6: "unknown_source", 7: "unknown_target"}
+TEXT_STRICT_FLAG = 4
+
+
+def scattered_signatures():
+    """argtypes of the bvg_scattered_* entry points (arc lists of arbitrary identifiers), by name."""
+    vp, i64, u64, pp, ci, u32 = C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(C.c_void_p), C.c_int, C.c_uint32
+    args = [vp, u64, u32, vp, i64, ci, pp, C.POINTER(ScatteredReport), C.POINTER(TextError)]
+    return {"bvg_scattered_parse": list(args), "bvg_scattered_parse_dev": list(args), "bvg_scattered_ids": [vp, vp, u64], "bvg_scattered_ids_dev": [vp, vp, u64]}
+
+
 class TransformSrc(C.Structure):
     """bvg_transform_src: exactly one of the two handles is set."""
     _fields_ = [("graph", C.c_void_p), ("csr", C.c_void_p)]

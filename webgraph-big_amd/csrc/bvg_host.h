@@ -232,6 +232,7 @@ struct bvg_text {
     DevArray<uint64_t> d_off;           // adj_off[nodes + 1]
     int64_t* d_adj = nullptr;           // adj[arcs], inside adj_base
     DevArray<int64_t> adj_base;
+    DevArray<int64_t> ids;              // ids[nodes]: the identifier of every node (bvg_scattered.hip); empty for every other producer
     ~bvg_text() { (void)hipSetDevice(device); }
 };
 

@@ -578,6 +578,30 @@ inline std::unique_ptr<ParsedGraph> loadArcList(const std::string& text, int64_t
     const int st = bvg_text_parse_arcs(text.data(), text.size(), shift, (symmetrize ? BVG_TEXT_SYMMETRIZE : 0u) | (noLoops ? BVG_TEXT_NO_LOOPS : 0u), minNodes, device, &t, &e);
     return finishParse(st, t, e, "loadArcList");
 }
+// ScatteredArcsASCIIGraph on a text in memory: `source target` lines whose identifiers are any integers of [-2^63, 2^63).  Every newly seen
+// identifier gets the next node number (ids()[node] is the identifier), offending lines are counted in report() and skipped -- refused
+// (TextRefusal, reason BVG_SCATTERED_*) with strict.  knownIds: a numbering given in advance; lines that mention other identifiers are skipped.
+class ScatteredGraph : public ParsedGraph {
+    bvg_scattered_report rep_;
+public:
+    ScatteredGraph(bvg_text* t, const bvg_scattered_report& rep) : ParsedGraph(t), rep_(rep) {}
+    const bvg_scattered_report& report() const { return rep_; }
+    std::vector<int64_t> ids() const {
+        std::vector<int64_t> v((size_t)numNodes());
+        check(bvg_scattered_ids(handle(), v.empty() ? nullptr : v.data(), v.size()), "scattered_ids");
+        return v;
+    }
+};
+inline std::unique_ptr<ScatteredGraph> parseScatteredArcs(const std::string& text, bool symmetrize = false, bool noLoops = false, const std::vector<int64_t>* knownIds = nullptr,
+                                                          bool strict = false, int device = 0) {
+    bvg_text* t = nullptr; bvg_text_error e{}; bvg_scattered_report rep{};
+    static const int64_t none = 0;
+    const int st = bvg_scattered_parse(text.data(), text.size(), (symmetrize ? BVG_TEXT_SYMMETRIZE : 0u) | (noLoops ? BVG_TEXT_NO_LOOPS : 0u) | (strict ? BVG_TEXT_STRICT : 0u),
+                                       knownIds ? (knownIds->empty() ? &none : knownIds->data()) : nullptr, knownIds ? (int64_t)knownIds->size() : 0, device, &t, &rep, &e);
+    if (st != BVG_OK && e.reason != 0) throw TextRefusal(st, e, "parseScatteredArcs");
+    check(st, "parseScatteredArcs");
+    return std::unique_ptr<ScatteredGraph>(new ScatteredGraph(t, rep));
+}
 // the lines of nodes [from, to) as ASCIIGraph.store writes them (never a header line), and their arcs as ArcListASCIIGraph.store writes them
 inline std::string formatASCIIGraph(BVGraph& g, int64_t from, int64_t to) {
     uint64_t need = 0;

@@ -1,6 +1,7 @@
 """Text graphs over the C ABI (include/bvgraph_hip.h, bvg_text_*): ASCIIGraph (basename.graph-txt) and arc lists, read into a CSR
-that stays on the device and written from a BVGraph, an EFGraph or an adjacency; BVGraph.store to disk (write_bvgraph); and the command
-lines of ASCIIGraph.main, ArcListASCIIGraph.main and BVGraph.main (BVGraph.java:2613-2715)."""
+that stays on the device and written from a BVGraph, an EFGraph or an adjacency; arc lists of arbitrary numeric identifiers
+(bvg_scattered_*: ScatteredArcsASCIIGraph); BVGraph.store to disk (write_bvgraph); and the command lines of ASCIIGraph.main,
+ArcListASCIIGraph.main, BVGraph.main (BVGraph.java:2613-2715) and ScatteredArcsASCIIGraph.main."""
 import argparse
 import ctypes as C
 import gzip
@@ -167,6 +168,89 @@ def load_arc_list(path, shift=0, symmetrize=False, no_loops=False, min_nodes=0, 
     if not os.path.isfile(path):
         raise _EXC[_abi.E_IO](_abi.E_IO, "load_arc_list(%s)" % path)
     return parse_arc_list(_read(path), shift, symmetrize, no_loops, min_nodes, device)
+
+
+# ---- scattered arc lists: identifiers that are not node numbers (bvg_scattered_*)
+
+def _scattered_fns():
+    """The bvg_scattered_* entry points, bound on first use."""
+    L = _text_fns()
+    if getattr(L, "_scattered_bound", False):
+        return L
+    for name, args in _abi.scattered_signatures().items():
+        if not hasattr(L, name):
+            raise UnsupportedOperationException(_abi.E_UNSUPPORTED, name + " is not in this build of the library")
+        getattr(L, name).argtypes = args
+    L._scattered_bound = True
+    return L
+
+
+class ScatteredGraph(ParsedGraph):
+    """A parsed scattered arc list: a ParsedGraph (store(), the transforms and compose take it) with .ids, int64[nodes], the identifier of
+    every node, and .report, what the parser saw (a dict of bvg_scattered_report's fields; first_reason a name of _abi.SCATTERED_REASONS
+    or None)."""
+
+    def __init__(self, handle, report, device=0):
+        ParsedGraph.__init__(self, handle, device)
+        self.report = report.as_dict()
+        self._ids = None
+
+    @property
+    def ids(self):
+        if self._ids is None:
+            ids = np.empty(self._n, dtype=np.int64)
+            _check(_scattered_fns().bvg_scattered_ids(self._h, ids.ctypes.data if self._n else None, self._n), "scattered_ids")
+            self._ids = ids
+        return self._ids
+
+    def ids_dev(self, ptr, cap):
+        """bvg_scattered_ids_dev: into a device buffer (capacity in elements)."""
+        _check(_scattered_fns().bvg_scattered_ids_dev(self._h, ptr, cap), "scattered_ids_dev")
+
+
+def _check_scattered(status, err, rep, what):
+    """As _check_text, the reason being a name of _abi.SCATTERED_REASONS; the exception carries .report as well."""
+    if status == 0:
+        return
+    if err.reason == 0:
+        _check(status, what)
+    reason = _abi.SCATTERED_REASONS.get(err.reason, str(err.reason))
+    e = _EXC.get(status, BVGraphError)(status, "%s: %s at line %d, byte %d" % (what, reason.replace("_", " "), err.line, err.byte))
+    e.line, e.byte, e.reason, e.reason_code, e.report = int(err.line), int(err.byte), reason, int(err.reason), rep.as_dict()
+    raise e
+
+
+def _scattered_flags(symmetrize, no_loops, strict):
+    return _arc_flags(symmetrize, no_loops) | (_abi.TEXT_STRICT_FLAG if strict else 0)
+
+
+def parse_scattered_arcs(data, symmetrize=False, no_loops=False, ids=None, strict=False, device=0):
+    """`source target` lines whose identifiers are any integers of [-2^63, 2^63) -> ScatteredGraph: every newly seen identifier gets the next
+    node number, offending lines are counted and skipped (strict=True: refused).  ids: a numbering given in advance (node i has identifier
+    ids[i]); lines that mention other identifiers are skipped."""
+    b = _bytes_of(data)
+    known = None if ids is None else np.ascontiguousarray(ids, dtype=np.int64)
+    h = C.c_void_p(); err = TextError(); rep = _abi.ScatteredReport()
+    pad = np.zeros(1, dtype=np.int64)                                       # (a pointer that is not NULL for an empty numbering)
+    st = _scattered_fns().bvg_scattered_parse(b.ctypes.data if len(b) else None, len(b), _scattered_flags(symmetrize, no_loops, strict),
+                                              None if known is None else (known.ctypes.data if len(known) else pad.ctypes.data), 0 if known is None else len(known),
+                                              device, C.byref(h), C.byref(rep), C.byref(err))
+    _check_scattered(st, err, rep, "parse_scattered_arcs")
+    return ScatteredGraph(h, rep, device)
+
+
+def parse_scattered_arcs_dev(ptr, nbytes, symmetrize=False, no_loops=False, ids_ptr=None, n_ids=0, strict=False, device=0):
+    """The text, and the given numbering if any, in device memory."""
+    h = C.c_void_p(); err = TextError(); rep = _abi.ScatteredReport()
+    st = _scattered_fns().bvg_scattered_parse_dev(ptr, nbytes, _scattered_flags(symmetrize, no_loops, strict), ids_ptr, n_ids, device, C.byref(h), C.byref(rep), C.byref(err))
+    _check_scattered(st, err, rep, "parse_scattered_arcs_dev")
+    return ScatteredGraph(h, rep, device)
+
+
+def load_scattered_arcs(path, symmetrize=False, no_loops=False, ids=None, strict=False, device=0):
+    if not os.path.isfile(path):
+        raise _EXC[_abi.E_IO](_abi.E_IO, "load_scattered_arcs(%s)" % path)
+    return parse_scattered_arcs(_read(path), symmetrize, no_loops, ids, strict, device)
 
 
 def _sized_text(call, what):
@@ -490,4 +574,75 @@ def bvgraph_main(argv=None):
             write_bvgraph(a.destBasename, (off, succ), p, 0, a.device)
     finally:
         src.close()
+    return 0
+
+
+def scattered_arg_parser():
+    ap = argparse.ArgumentParser(prog="scattered_main", description="Reads a list of arcs whose identifiers are arbitrary integers from standard input (or --input) and "
+                                 "compresses it as a BVGraph; writes basename.ids, the identifier of every node (ScatteredArcsASCIIGraph.main: its option letters).")
+    ap.add_argument("-S", "--symmetrize", action="store_true", help="Force the output graph to be symmetric.")
+    ap.add_argument("-L", "--no-loops", dest="no_loops", action="store_true", help="Remove loops from the output graph.")
+    ap.add_argument("-z", "--zipped", action="store_true", help="The list of arcs is compressed in gzip format.")
+    ap.add_argument("-w", "--window-size", dest="window_size", type=int, default=7)
+    ap.add_argument("-m", "--max-ref-count", dest="max_ref_count", type=int, default=3)
+    ap.add_argument("-i", "--min-interval-length", dest="min_interval_length", type=int, default=4)
+    ap.add_argument("-k", "--zeta-k", dest="zeta_k", type=int, default=3)
+    ap.add_argument("-c", "--comp", dest="comp", action="append", default=[], help="A compression flag (may be specified several times), e.g. RESIDUALS_GAMMA.")
+    ap.add_argument("--ids", help="A file of longs in BinIO format: node i has identifier ids[i] (lines that mention others are skipped; no basename.ids is written).")
+    ap.add_argument("--strict", action="store_true", help="Refuse the input at its first offending line.")
+    ap.add_argument("--input", help="Read the arcs from this file in place of standard input (a name ending in .gz goes through gzip).")
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("basename")
+    return ap
+
+
+def scattered_main(argv=None):
+    """ScatteredArcsASCIIGraph.main: [-S] [-L] [-z] [-w W] [-m M] [-i I] [-k K] [-c FLAG]... [--ids FILE] [--input FILE] basename.  The
+    translation function of the reference (-f, -b, -C, -n) is for string identifiers, which are not built: refused with a message, as its
+    other options are.  The counts of the report go to standard error, where the reference logs."""
+    argv = sys.argv[1:] if argv is None else list(argv)
+    for opt in ("-f", "--function", "-b", "--byte-array", "-C", "--charset", "-n", "--n"):
+        if any(x == opt or (opt.startswith("--") and x.startswith(opt + "=")) for x in argv):
+            print("scattered_main: %s belongs to the translation function for string identifiers, which is not supported here (numeric identifiers: --ids FILE)" % opt, file=sys.stderr)
+            return 1
+    a = _parse(scattered_arg_parser(), argv, "scattered_main")
+    if a is None:
+        return 1
+    p = _abi.default_params(window_size=a.window_size, max_ref_count=a.max_ref_count, min_interval_length=a.min_interval_length, zeta_k=a.zeta_k)
+    names = {v: k for k, v in _CODING_NAMES.items()}
+    for flag in a.comp:
+        for f, prefix in _FLAG_FIELDS:
+            if flag.startswith(prefix) and flag[len(prefix):] in names:
+                setattr(p, f, names[flag[len(prefix):]])
+                break
+        else:
+            print("scattered_main: unknown compression flag %r" % flag, file=sys.stderr)
+            return 1
+    if a.input is not None:
+        if not os.path.isfile(a.input):
+            raise _EXC[_abi.E_IO](_abi.E_IO, "scattered_main(%s)" % a.input)
+        data = _read(a.input)
+    else:
+        data = sys.stdin.buffer.read()
+    if a.zipped and not (a.input or "").endswith(".gz"):
+        data = gzip.decompress(data)
+    known = None
+    if a.ids is not None:
+        if not os.path.isfile(a.ids):
+            raise _EXC[_abi.E_IO](_abi.E_IO, "scattered_main(%s)" % a.ids)
+        known = np.fromfile(a.ids, dtype=">i8").astype(np.int64)            # (BinIO.loadLongs)
+    g = parse_scattered_arcs(data, a.symmetrize, a.no_loops, known, a.strict, a.device)
+    try:
+        r = g.report
+        print("scattered_main: %d lines, %d arcs kept, %d nodes, %d arcs in the graph" % (r["lines"], r["arcs"], g.num_nodes(), g.num_arcs()), file=sys.stderr)
+        for k in ("bad_source", "bad_target", "no_target", "too_large", "trailing", "unknown_source", "unknown_target", "dropped_loops"):
+            if r[k]:
+                print("scattered_main: %s: %d lines" % (k.replace("_", " "), r[k]), file=sys.stderr)
+        if r["first_reason"]:
+            print("scattered_main: the first offending line is line %d (byte %d): %s" % (r["first_line"], r["first_byte"], r["first_reason"].replace("_", " ")), file=sys.stderr)
+        write_bvgraph(a.basename, g, p, 0, a.device)
+        if known is None:
+            g.ids.astype(">i8").tofile(a.basename + ".ids")                # (BinIO.storeLongs)
+    finally:
+        g.close()
     return 0
